@@ -21,10 +21,19 @@ anything in this process touches the GPU), forwards rank 0's JSON line and exits
 non-zero if any rank fails.  The line carries `rccl_world` (the process group's
 own world size after init) and every rank's timed-region seconds.
 
-Extra JSON fields: `roofline` (dominant kernel, HIP-event timed on its stream),
-`cpu_baseline` (the CPU restatement of the reference algorithm — dense Laplacian
-matvec + per-point scalar KAN — timed on this host, rank 0 at N=1), `vjp` (the
-adjoint kernel's rate, measured after the timed region).
+A plain run sets up, warms up, times the steps and prints the line: `value`,
+`ms_per_step` (wall milliseconds per timed step) and `roofline` (the dominant
+kernel, from one HIP-event pair around the same timed steps).  `--dump-outputs DIR`
+also writes what the last timed step computed, du, as DIR/du.npy (DIR/du_rank<r>.npy
+per rank at N > 1): fp64, a fixed seeded sample of its trajectories when the whole
+would pass 32 MiB.  The inputs are seeded, so two builds can be compared array for array.
+
+`--full` adds every secondary leg after the timed region, each a run of its own:
+`roofline.torch_copy_GBps` (a device copy of the same bytes), `shard_ceiling`, `vjp`
+(the adjoint kernel's rate), the LV / FK26 / surrogate training legs, `epoch` and
+`epoch_adaptive`, the multi-rank surrogates at N > 1, and `cpu_baseline` (the CPU
+restatement of the reference algorithm — dense Laplacian matvec + per-point scalar
+KAN — timed on this host, rank 0 at N=1).  The `--no-*` options choose among them.
 """
 from __future__ import annotations
 
@@ -741,6 +750,27 @@ def surrogate_dist_bench(dev, rank: int, world: int, backend: str, reps: int = 2
     return out
 
 
+DUMP_MAX_BYTES = 32 << 20      # everything one --dump-outputs run writes, over all ranks
+DUMP_SEED = 20240
+
+
+def dump_outputs(directory: str, name: str, x: torch.Tensor, max_bytes: int) -> dict:
+    """Write the (B, n) result `x` of the last timed step as directory/name.npy (its own dtype, fp64 here).  A
+    result above max_bytes is written as a fixed sample of its trajectories: the first, the last and a
+    seeded draw of the rest, in ascending order, the same rows for the same shape in every run."""
+    os.makedirs(directory, exist_ok=True)
+    B = x.shape[0]
+    rows = max(2, max_bytes // (x[0].numel() * x.element_size()))
+    if rows < B:
+        pick = np.random.default_rng(DUMP_SEED).choice(B - 2, size=rows - 2, replace=False) + 1
+        idx = np.sort(np.concatenate([[0, B - 1], pick]))
+        x = x.index_select(0, torch.as_tensor(idx, device=x.device))
+    a = x.cpu().numpy()
+    np.save(os.path.join(directory, name + ".npy"), a)
+    return {"name": name, "shape": list(a.shape), "of_trajectories": B, "dtype": str(a.dtype),
+            "sample": "whole" if a.shape[0] == B else f"first, last and a seeded draw (seed {DUMP_SEED}), ascending"}
+
+
 LAUNCH_ENV = "KANODE_BENCH_LAUNCH"      # set by launch_ranks in the children it starts
 
 
@@ -836,6 +866,13 @@ def main() -> None:
                          "would mix into a kernel-trace summary of the 1M-trajectory launch)")
     ap.add_argument("--grid-rhs", type=int, default=0,
                     help="tuning: persistent grid of the table RHS kernel (KANODE_OPT_GRID_RHS; 0 = default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary leg (streaming-copy reference, shard_ceiling, "
+                         "VJP rate, LV / FK26 / surrogate training legs, epochs, multi-rank surrogates, CPU baselines); "
+                         "the --no-* options above select among them.  Without it the run is the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (du, or a fixed seeded sample of its trajectories) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
 
     mode, world = resolve_world(args.gpus, os.environ)
@@ -924,20 +961,27 @@ def main() -> None:
         rank_elapsed = [float(t.item()) for t in allt]
         elapsed = max(rank_elapsed)
     kern_ms = e_beg.elapsed_time(e_end) / args.steps
-    # this box's streaming reference: a device copy moving the same bytes (u -> du)
-    c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    du.copy_(u)
-    c0.record(stream)
-    for _ in range(5):
+    dumped = None
+    if args.dump_outputs:
+        # du still holds the last timed step's result: written before any later leg reuses the buffer
+        dumped = dump_outputs(args.dump_outputs, "du" if world == 1 else f"du_rank{rank}", du,
+                              DUMP_MAX_BYTES // world)
+    copy_gbps = None
+    if args.full:
+        # this host's streaming reference: a device copy moving the same bytes (u -> du)
+        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         du.copy_(u)
-    c1.record(stream)
-    torch.cuda.synchronize()
-    copy_gbps = 16.0 * B * nx / (c0.elapsed_time(c1) / 5 * 1e-3) / 1e9
+        c0.record(stream)
+        for _ in range(5):
+            du.copy_(u)
+        c1.record(stream)
+        torch.cuda.synchronize()
+        copy_gbps = 16.0 * B * nx / (c0.elapsed_time(c1) / 5 * 1e-3) / 1e9
 
     total_evals = B * args.steps * world
     value = total_evals / elapsed
     ceiling = None
-    if world == 1 and not weak and not args.no_shard_ceiling:
+    if args.full and world == 1 and not weak and not args.no_shard_ceiling:
         ceiling = shard_ceiling(rhs, u, du, ps, stream, args.steps, B / (kern_ms * 1e-3))
     alg_bytes = 8.0 * (rhs.P + B * (nx + nx))       # p + u in + du out, per launch
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
@@ -965,6 +1009,8 @@ def main() -> None:
         "launch": ("self-spawned ranks (bench.py --gpus)" if os.environ.get(LAUNCH_ENV) == "self"
                    else "external launcher (WORLD_SIZE)") if dist else "single process",
         "rank_timed_s": rank_elapsed,
+        "full": args.full,
+        "dumped_outputs": dumped,
         "shard_ceiling": ceiling,
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
@@ -975,7 +1021,7 @@ def main() -> None:
                      "torch_copy_GBps": copy_gbps},
     }
 
-    if not args.no_vjp:
+    if args.full and not args.no_vjp:
         lam = torch.randn_like(u)
         lamJ = torch.empty_like(u)
         dp = torch.zeros_like(p)
@@ -1001,14 +1047,14 @@ def main() -> None:
         out["vjp"] = {"value": B * world / (vms * 1e-3), "unit": "VJP-evals/s", "ms_per_step": vms,
                       "achieved_GBps": vbytes / (vms * 1e-3) / 1e9}
 
-    if rank == 0 and not args.no_vjp:
+    if args.full and rank == 0 and not args.no_vjp:
         out["lv4096"] = lv4096_bench(dev)
         out["lv1_train"] = lv1_train_bench(dev, world == 1 and not args.no_cpu_baseline)
         out["lv4096_train"] = lv4096_train_bench(dev, world == 1 and not args.no_cpu_baseline)
         out["fk26_train"] = fk26_train_bench(dev, world == 1 and not args.no_cpu_baseline)
         out["surrogates"] = surrogate_bench(dev, world == 1 and not args.no_cpu_baseline)
 
-    if not args.no_epoch:
+    if args.full and not args.no_epoch:
         ep = epoch_bench(dev, p_np, nx, dx, D, args.epoch_batch, 0 if (args.no_cpu_baseline or world > 1) else 16,
                          args.epoch_steps, 1e-3, 3, group=tdist.group.WORLD if dist else None, rank=rank,
                          world=world)
@@ -1018,7 +1064,7 @@ def main() -> None:
             out["epoch_adaptive"] = epoch_adaptive_bench(dev, fk_trained_like_params(), nx, dx, D, args.epoch_batch,
                                                          0 if (args.no_cpu_baseline or world > 1) else 2)
 
-    if dist and not args.no_dist_surrogates:
+    if args.full and dist and not args.no_dist_surrogates:
         # a secondary leg: an exception here is recorded in the line instead of taking the metric above
         # down with it.  Every rank then all-reduces a failure flag before any further collective, so a
         # rank that failed alone (an allocation, a HIP error on one GPU) does not leave the others
@@ -1038,7 +1084,7 @@ def main() -> None:
         if rank == 0:
             out.update(sd)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline(nx, dx, D, p_np, args.cpu_seconds)
         out["cpu_baseline"] = cb
         out["gpu_vs_cpu"] = value / cb["value"]

@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # Round evidence on the GPU box -> gpurun_out/profile_$TAG/ (copied into profiles/$TAG by the caller):
 #   0. pytest -m gpu (whole suite) and __graft_entry__.smoke()
-#   1. bench.py (the driver's command, with cpu_baseline)  -> bench.json
+#   1. bench.py --full (every leg, with cpu_baseline)      -> bench.json
 #   2. rocprofv3 --kernel-trace --stats of the same bench    -> kernel_stats.csv
 #   3. separate --pmc passes (no trace domains with PMC): FETCH_SIZE, WRITE_SIZE, VALU counters
 #   4. tools/traffic.py -> traffic.json (gfx950: FETCH_SIZE x2 for 16-B/lane streaming reads)
@@ -18,11 +18,11 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   tail -2 $OUT/smoke.log
 fi
 echo "== bench"
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 3; }
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 3; }
 cat $OUT/bench.json
 echo "== kernel trace"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- \
-  python3 bench.py --no-cpu-baseline > $OUT/trace.log 2>&1 || { tail -5 $OUT/trace.log; exit 3; }
+  python3 bench.py --full --no-cpu-baseline > $OUT/trace.log 2>&1 || { tail -5 $OUT/trace.log; exit 3; }
 cp $OUT/trace/run_kernel_stats.csv $OUT/kernel_stats.csv
 for w in fk_rhs fk_rhs_rec fk_vjp; do
   for c in FETCH_SIZE WRITE_SIZE "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_LDS"; do
