@@ -376,11 +376,11 @@ kanode_status kanode_forward_sensitivity_tsit5(kanode_handle* h, const void* p, 
                                                double t0, double tf, const double* saveat, int64_t n_save,
                                                void* u_save, void* s_save, const kanode_solver_options* opt,
                                                kanode_solve_stats* stats, void* stream);
-/* 1 when kanode_forward_sensitivity_tsit5 covers this handle at `batch` trajectories, else 0 (no GPU work). */
 /* The accepted steps of the handle's last kanode_forward_sensitivity_tsit5 (until the next solve without a dense output
  * on the handle): ts[i], dts[i] for i < min(count, cap) (host arrays, either NULL); returns the count (the first 4096
  * steps are recorded), -1 for a NULL handle.  Diagnostics: another solver can replay the same step sequence. */
 int64_t kanode_forward_sensitivity_step_sizes(kanode_handle* h, double* ts, double* dts, int64_t cap);
+/* 1 when kanode_forward_sensitivity_tsit5 covers this handle at `batch` trajectories, else 0 (no GPU work). */
 int32_t kanode_forward_sensitivity_supported(const kanode_handle* h, int64_t batch);
 /* KANODE_OPT_RECORD_ADJOINT_STEPS: the accepted step sizes of the handle's last kanode_adjoint_tsit5
  * (in backward order), out[i] for i < min(count, cap) (out may be NULL).  Returns the count (0 when not
@@ -404,6 +404,54 @@ kanode_status kanode_table_rejections(kanode_handle* h, int32_t out[3]);
 kanode_status kanode_adam_step(void* x, void* m, void* v, const void* g, int64_t n, int32_t dtype, double scale,
                                double eta, double beta1, double beta2, double eps, double beta1_t, double beta2_t,
                                void* stream);
+
+/* --- the device-resident training loop of one Lotka-Volterra trajectory -------------------------
+ * n_iters whole iterations of the reference's driver loop (LV_driver_KANODE.jl:279-291) in ONE kernel launch,
+ * the host nowhere in between.  Iteration it = 0 .. n_iters-1, in order:
+ *     forward Tsit5 solve at p_it over (t0, tf), saved at saveat          (kanode_solve_tsit5's arithmetic)
+ *     loss[it] = mean((u_save - target)²)                                 -- the loss AT p_it, before the update
+ *     dp = InterpolatingAdjoint of it, dl_du = (u_save - target)·2/numel  (kanode_adjoint_tsit5's)
+ *     p, m, v <- Adam(p_it, m, v, dp) with the running powers βp          (kanode_adam_step's, scale = 1)
+ *     loss_test[it] = mean((u(saveat_test) - target_test)²) of a solve over (t0, tf_test) at p_{it+1},
+ *                     the parameters AFTER the update                      (when a test problem is given)
+ * beta1_t, beta2_t are the running powers on entry (β for a fresh optimiser); they advance on the device by one
+ * product with β per iteration, and the caller advances its own copy by *iters_done products afterwards.
+ *
+ * Covered (kanode_train_supported): an fp64 chain [2 -> 10 -> 2], G = 5, rbf basis, base activation on both
+ * layers, tanh_fast or softsign, batch = 1, with KANODE_OPT_FUSED_SOLVE and KANODE_OPT_CHAIN_WIDE on -- the shapes
+ * whose adjoint is the stage-parallel one-workgroup kernel.  Anything else: KANODE_ERR_UNSUPPORTED, nothing
+ * launched.  opt->control is ignored.
+ *
+ * Ownership: p, m, v ([P], device) are the caller's and are updated in place; u0 ([2]), target ([n_save][2]) and
+ * target_test ([n_save_test][2]) are device arrays the call only reads; saveat and saveat_test are host arrays
+ * (ascending, within [t0, tf] / [t0, tf_test]).  No test problem: n_save_test = 0 (saveat_test, target_test and
+ * loss_test may be NULL).  Device outputs, each written for the iterations that ran: loss [n_iters], loss_test
+ * [n_iters] (nullable) and three nullable per-iteration records, grad [n_iters][P] (dp of iteration it),
+ * p_before [n_iters][P] (p_it) and counts [n_iters][4] (int64: forward naccept, nreject, adjoint naccept,
+ * nreject).  The saveat copies, the adjoint's jump groups and the dense-output block live on the handle and are
+ * reused by later calls.  One forward solve may keep KANODE_OPT_FUSED_SOLVE_CAP accepted steps (at most 1024;
+ * default: as many as keep the dense output in LDS).
+ *
+ * A failing iteration stops the loop BEFORE its Adam step, p, m, v left as the last good iteration made them:
+ * *iters_done (host) = the iterations completed, *stop_reason (host) = a kanode_train_stop.  The call synchronises
+ * the stream; it returns KANODE_OK with *iters_done = n_iters, or KANODE_ERR_INVALID_ARG with the iteration and
+ * reason in kanode_last_error.  A capturing stream is refused (KANODE_ERR_CAPTURE). */
+typedef enum {
+    KANODE_TRAIN_OK = 0,
+    KANODE_TRAIN_FORWARD_MAXITERS = 1,   /* the forward solve reached opt->maxiters */
+    KANODE_TRAIN_DENSE_CAPACITY = 2,     /* a forward solve accepted more steps than the dense output holds */
+    KANODE_TRAIN_ADJOINT_MAXITERS = 3,   /* the adjoint reached opt->maxiters */
+    KANODE_TRAIN_LOSS_NOT_FINITE = 4,
+    KANODE_TRAIN_TEST_MAXITERS = 5       /* the test-loss solve reached opt->maxiters (its iteration's update is kept) */
+} kanode_train_stop;
+int32_t kanode_train_supported(const kanode_handle* h, int64_t batch);
+kanode_status kanode_train_tsit5(kanode_handle* h, void* p, void* m, void* v, const void* u0, int64_t batch,
+                                 double t0, double tf, const double* saveat, int64_t n_save, const void* target,
+                                 double tf_test, const double* saveat_test, int64_t n_save_test,
+                                 const void* target_test, const kanode_solver_options* opt, double eta,
+                                 double beta1, double beta2, double eps, double beta1_t, double beta2_t,
+                                 int64_t n_iters, double* loss, double* loss_test, void* grad, void* p_before,
+                                 int64_t* counts, int64_t* iters_done, int32_t* stop_reason, void* stream);
 
 /* --- the data-parallel gradient all-reduce (one process per GPU) -----------------
  * For hosts without a collective of their own (Julia, C): after kanode_adjoint_tsit5 on each rank's

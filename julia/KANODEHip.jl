@@ -430,6 +430,38 @@ function ChainRulesCore.rrule(::typeof(solve_tsit5_fwd), h::Handle, u0::Abstract
     return sol, solve_tsit5_fwd_pullback
 end
 
+# --- the device-resident training loop (kanode_train_tsit5): n_iters iterations of LV_driver_KANODE.jl:279-291
+# (forward solve, loss, InterpolatingAdjoint, Flux Adam, test-loss solve) in one kernel launch.  p, m, v, u0, target
+# and the outputs are device pointers (upload / DevBuf); saveat lists are host vectors.  βp: Flux's running powers
+# (opt.state[p][3]) on entry; advance them by the returned iteration count afterwards.
+train_supported(h::Handle, B::Integer) = ccall(sym(:kanode_train_supported), Int32, (Ptr{Cvoid}, Int64), h.ptr, B) == 1
+
+"""train_tsit5!(h, p, m, v, u0, tspan, saveat, target, n_iters, loss; η, β, ϵ, βp, test, loss_test, grad, p_before,
+counts, opt) -> (iters_done, stop_reason).  loss[it] is the loss at p_it (before the update), loss_test[it] at
+p_{it+1}; test = (tf_test, saveat_test, target_test).  A stopped loop (stop_reason != 0: a kanode_train_stop)
+returns normally with p, m, v as the last good iteration left them; any other failure throws."""
+function train_tsit5!(h::Handle, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cvoid}, u0::Ptr{Cvoid}, tspan,
+                      saveat::Vector{Float64}, target::Ptr{Cvoid}, n_iters::Integer, loss::Ptr{Cvoid};
+                      η::Real = 1e-3, β = (0.9, 0.999), ϵ::Real = 1e-8, βp = β, test = nothing,
+                      loss_test::Ptr{Cvoid} = C_NULL, grad::Ptr{Cvoid} = C_NULL, p_before::Ptr{Cvoid} = C_NULL,
+                      counts::Ptr{Cvoid} = C_NULL, opt::SolverOptions = default_options(),
+                      stream::Ptr{Cvoid} = C_NULL)
+    train_supported(h, 1) || throw(ArgumentError("train_tsit5!: not covered for this handle"))
+    issorted(saveat) || throw(ArgumentError("saveat must be ascending"))
+    tf_t, sv_t, tg_t = test === nothing ? (0.0, Float64[], Ptr{Cvoid}(C_NULL)) : (Float64(test[1]), Vector{Float64}(test[2]), test[3])
+    done = Ref{Int64}(0)
+    stop = Ref{Int32}(0)
+    st = GC.@preserve saveat sv_t ccall(sym(:kanode_train_tsit5), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float64}, Int64,
+         Ptr{Cvoid}, Float64, Ptr{Float64}, Int64, Ptr{Cvoid}, Ref{SolverOptions}, Float64, Float64, Float64, Float64,
+         Float64, Float64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}, Ref{Int32},
+         Ptr{Cvoid}),
+        h.ptr, p, m, v, u0, 1, tspan[1], tspan[2], saveat, length(saveat), target, tf_t, sv_t, length(sv_t), tg_t,
+        opt, η, β[1], β[2], ϵ, βp[1], βp[2], n_iters, loss, loss_test, grad, p_before, counts, done, stop, stream)
+    stop[] == 0 && check(h, st)
+    return done[], stop[]
+end
+
 # --- data-parallel training across GPUs (kanode_comm_*): one process per GPU, each with its trajectory
 # shard; after the adjoint, the flat [dp; L] (device) is SUM all-reduced over RCCL and the mean applied by
 # kanode_adam_step(scale = 1/nranks).  Rank 0 calls comm_unique_id() and the host distributes the bytes

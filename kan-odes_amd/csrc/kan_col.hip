@@ -1689,57 +1689,50 @@ kd_chain_adjoint_lvwave_kernel(const LayerConst* __restrict__ lcs, const T* __re
 constexpr int kLvSpWaves = 6;   // the stage waves; one more takes the controller's qold^β2 during the stage phase
 constexpr int kLvP = LvWaveShape::F1 * LvWaveShape::H + LvWaveShape::F2 * LvWaveShape::O;   // 240
 constexpr int kLvPL = (kLvP + kWave - 1) / kWave;                                               // μ entries per lane
-template <int NORM>
-__global__ void __launch_bounds__((kLvSpWaves + 1) * kWave)
-kd_chain_adjoint_lvsp_kernel(const LayerConst* __restrict__ lcs, const double* __restrict__ p, ChainAdjointArgs a,
-                             int stage_rec) {
-    using K = Tsit5Tab;
-#define KAN_LVSP_POW(x, y) KAN_ONEWG_POW(x, y)
-    constexpr int N = LvWaveShape::I, P = kLvP, RW = P + N;   // a row: G_k (P), then J_k (N)
-    extern __shared__ __attribute__((aligned(16))) unsigned char cv_raw[];
-    LayerConst* lcl = reinterpret_cast<LayerConst*>(cv_raw);
-    double* ps = reinterpret_cast<double*>(cv_raw + 2 * sizeof(LayerConst));
-    double* tsl = ps + P;
-    double* dtsl = tsl + a.nsteps;
-    __shared__ double jst[6][N][RW];   // this step's stage points: row k of [G | J] at stage i
-    __shared__ double jfs[2][N][RW];   // the step's first point (FSAL), by parity
-    __shared__ double pqs;             // qold^β2 of this step (the last wave)
+// The kernel's static LDS (a row of [G | J]: G_k (P entries), then J_k (N))
+struct LvSpLds {
+    static constexpr int N = LvWaveShape::I, RW = kLvP + LvWaveShape::I;
+    double jst[6][N][RW];   // this step's stage points: row k of [G | J] at stage i
+    double jfs[2][N][RW];   // the step's first point (FSAL), by parity
+    double pqs;             // qold^β2 of this step (the last wave)
     // the tableau in LDS (a_ij [6][6], b̃ [7], the interpolant's r_qm [7][4]): as compile-time literals the 71
     // fp64 constants were materialised once and held (then spilled) across the step loop; LDS reads of a
     // uniform address are broadcasts, re-issued after each barrier
-    __shared__ double kt[71];
-    for (int q = threadIdx.x; q < 71; q += blockDim.x)
-        kt[q] = q < 36 ? K::TA[q / 6][q % 6] : (q < 43 ? K::BT[q - 36] : K::RI[(q - 43) / 4][(q - 43) % 4]);
-    {
-        const int nw = 2 * (int)(sizeof(LayerConst) / sizeof(int32_t));
-        const int32_t* src = reinterpret_cast<const int32_t*>(lcs);
-        int32_t* dst = reinterpret_cast<int32_t*>(cv_raw);
-        stage_chain_consts(dst, src, nw, ps, p, P);
-        for (int64_t i = threadIdx.x; i < a.nsteps; i += blockDim.x) {
-            tsl[i] = a.ts[i];
-            dtsl[i] = a.dts[i];
-        }
+    double kt[71];
+    __device__ __forceinline__ void fill_tableau() {   // (published by the caller's next barrier)
+        using K = Tsit5Tab;
+        for (int q = threadIdx.x; q < 71; q += blockDim.x)
+            kt[q] = q < 36 ? K::TA[q / 6][q % 6] : (q < 43 ? K::BT[q - 36] : K::RI[(q - 43) / 4][(q - 43) % 4]);
     }
-    KAN_EXP_TABLE_LDS(tab);
-    const Math<double> M{tab};
-    const double* rec = reinterpret_cast<const double*>(a.rec);
-    const double* rk1 = reinterpret_cast<const double*>(a.k1_0);
-    if (stage_rec) {
-        double* recl = dtsl + a.nsteps;
-        onewg_stage_rec<double>(recl, a, N);
-        rec = recl;
-        rk1 = recl + a.nsteps * 7 * N;
-    }
+};
+// The adjoint itself, for the whole block of (kLvSpWaves + 1) waves: a's options, stops and jump groups; the
+// forward solve as nsteps, rec ([nsteps][7][N]), rk1 (k1_0) and tsl / dtsl (LDS), all of which may be device
+// state of the same launch (the fused training loop) -- a.rec, a.k1_0, a.ts, a.dts, a.nsteps and a's outputs are
+// not read.  Every wave returns the same λ(t0) (l0, l1) and counters res (naccept, nreject, nf, status); lane l
+// of every wave returns μ entries l + 64·r in mu[r].  Ends without a barrier.
+template <int NORM>
+__device__ __forceinline__ void lvsp_adjoint(LvSpLds& S, const Math<double>& M, const LayerConst* lcl,
+                                             const double* ps, const ChainAdjointArgs& a, const int64_t nsteps,
+                                             const double* rec, const double* rk1, const double* tsl,
+                                             const double* dtsl, double (&mu)[kLvPL], double& l0, double& l1,
+                                             int64_t (&res)[4]) {
+    using K = Tsit5Tab;
+#define KAN_LVSP_POW(x, y) KAN_ONEWG_POW(x, y)
+    constexpr int N = LvWaveShape::I, P = kLvP, RW = P + N;
+    auto& jst = S.jst;
+    auto& jfs = S.jfs;
+    double& pqs = S.pqs;
+    const double* kt = S.kt;
     LvWaveModel<double, NORM, true> m(M, lcl, ps, P);
     const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
     const double* dl = reinterpret_cast<const double*>(a.dl_du);
     const double t0 = a.t0, tf = a.tf, TT = tf - t0;
     const double ntot = (double)(N + P);
-    int64_t cur = a.nsteps - 1;   // this wave's forward interval
+    int64_t cur = nsteps - 1;   // this wave's forward interval
     auto interp = [&](double tau) -> double {   // u(tf - τ) on lanes < N (onewg_adjoint's adj)
         const double t = tf - tau;
         while (cur > 0 && tsl[cur] > t) --cur;
-        while (cur + 1 < a.nsteps && tsl[cur + 1] <= t) ++cur;
+        while (cur + 1 < nsteps && tsl[cur + 1] <= t) ++cur;
         const double dti = dtsl[cur];
         const double th = ::fmin(1.0, ::fmax(0.0, (t - tsl[cur]) / dti));
         const int c = lane < N ? lane : 0;
@@ -1787,7 +1780,8 @@ kd_chain_adjoint_lvsp_kernel(const LayerConst* __restrict__ lcs, const double* _
         const int q = lane + kWave * r;
         return q < P ? ::fma(s1, R[1][q], s0 * R[0][q]) : 0.0;
     };
-    double l0 = 0.0, l1 = 0.0;
+    l0 = 0.0;
+    l1 = 0.0;
     if (dl) jump(0, l0, l1);
     int fp = 0;
     if (w < kLvSpWaves) rows(0.0, w == 0 ? jfs[0] : jst[w]);   // (waves > 0: a scratch copy)
@@ -1795,7 +1789,6 @@ kd_chain_adjoint_lvsp_kernel(const LayerConst* __restrict__ lcs, const double* _
     double k10, k11;   // kλ_1
     kl_of(jfs[0], l0, l1, k10, k11);
     int64_t nf = 1;
-    double mu[kLvPL];
 #pragma unroll
     for (int r = 0; r < kLvPL; ++r) mu[r] = 0.0;
     double h = a.dt;
@@ -1937,6 +1930,48 @@ kd_chain_adjoint_lvsp_kernel(const LayerConst* __restrict__ lcs, const double* _
 #undef KAN_LVSP_POW
     if (it == a.maxiters && !(tau >= TT - 1e-14 * ::fmax(1.0, TT))) status = 1;
     if (dl) jump((int)a.nstops, l0, l1);
+    res[0] = naccept;
+    res[1] = nreject;
+    res[2] = nf;
+    res[3] = status;
+}
+
+template <int NORM>
+__global__ void __launch_bounds__((kLvSpWaves + 1) * kWave)
+kd_chain_adjoint_lvsp_kernel(const LayerConst* __restrict__ lcs, const double* __restrict__ p, ChainAdjointArgs a,
+                             int stage_rec) {
+    constexpr int N = LvWaveShape::I, P = kLvP;
+    extern __shared__ __attribute__((aligned(16))) unsigned char cv_raw[];
+    LayerConst* lcl = reinterpret_cast<LayerConst*>(cv_raw);
+    double* ps = reinterpret_cast<double*>(cv_raw + 2 * sizeof(LayerConst));
+    double* tsl = ps + P;
+    double* dtsl = tsl + a.nsteps;
+    __shared__ LvSpLds S;
+    S.fill_tableau();
+    {
+        const int nw = 2 * (int)(sizeof(LayerConst) / sizeof(int32_t));
+        const int32_t* src = reinterpret_cast<const int32_t*>(lcs);
+        int32_t* dst = reinterpret_cast<int32_t*>(cv_raw);
+        stage_chain_consts(dst, src, nw, ps, p, P);
+        for (int64_t i = threadIdx.x; i < a.nsteps; i += blockDim.x) {
+            tsl[i] = a.ts[i];
+            dtsl[i] = a.dts[i];
+        }
+    }
+    KAN_EXP_TABLE_LDS(tab);
+    const Math<double> M{tab};
+    const double* rec = reinterpret_cast<const double*>(a.rec);
+    const double* rk1 = reinterpret_cast<const double*>(a.k1_0);
+    if (stage_rec) {
+        double* recl = dtsl + a.nsteps;
+        onewg_stage_rec<double>(recl, a, N);
+        rec = recl;
+        rk1 = recl + a.nsteps * 7 * N;
+    }
+    double mu[kLvPL], l0, l1;
+    int64_t res[4];
+    lvsp_adjoint<NORM>(S, M, lcl, ps, a, a.nsteps, rec, rk1, tsl, dtsl, mu, l0, l1, res);
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
     if (w == 0) {
         if (a.du0 && lane < N) reinterpret_cast<double*>(a.du0)[lane] = lane == 0 ? l0 : l1;
         if (a.dp) {
@@ -1945,14 +1980,23 @@ kd_chain_adjoint_lvsp_kernel(const LayerConst* __restrict__ lcs, const double* _
                 if (lane + kWave * r < P) reinterpret_cast<double*>(a.dp)[lane + kWave * r] = mu[r];
         }
         if (lane == 0) {
-            a.out[0] = naccept;
-            a.out[1] = nreject;
-            a.out[2] = nf;
-            a.out[3] = status;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a.out[q] = res[q];
         }
     }
 }
 
+// one Lotka-Volterra trajectory on the LvWaveModel kernels (the lvsp / lvwave adjoints, the fused training loop)
+static bool chain_is_lv_wave(const LayerConst* hlcs, int nl, int64_t B, bool wide) {
+    return wide && B == 1 && nl == 2 && hlcs[0].use_base && hlcs[1].use_base && hlcs[0].norm == hlcs[1].norm &&
+           hlcs[0].I == LvWaveShape::I && hlcs[0].O == LvWaveShape::H && hlcs[1].I == LvWaveShape::H &&
+           hlcs[1].O == LvWaveShape::O && hlcs[0].G == LvWaveShape::G && hlcs[1].G == LvWaveShape::G &&
+           hlcs[0].basis == BASIS_RBF && hlcs[1].basis == BASIS_RBF &&
+           (hlcs[0].norm == NORM_TANH_FAST || hlcs[0].norm == NORM_SOFTSIGN);
+}
+
+// (kan_train.hip includes this file for the device code above and instantiates none of the launchers below)
+#ifndef KAN_COL_DEVICE_ONLY
 // The one-workgroup adjoint (kd_chain_adjoint_kernel): the small-chain conditions of
 // launch_kd_chain_tsit5 plus nsteps <= kChainAdjointMaxSteps and the LDS budget.
 template <typename T>
@@ -1962,11 +2006,7 @@ hipError_t launch_kd_chain_adjoint(const LayerConst* hlcs, int nl, const LayerCo
         a.nsteps > kChainAdjointMaxSteps)
         return hipErrorNotSupported;
     // one Lotka-Volterra trajectory: the chain on one wave (LvWaveModel)
-    if (wide && B == 1 && nl == 2 && hlcs[0].use_base && hlcs[1].use_base && hlcs[0].norm == hlcs[1].norm &&
-        hlcs[0].I == LvWaveShape::I && hlcs[0].O == LvWaveShape::H && hlcs[1].I == LvWaveShape::H &&
-        hlcs[1].O == LvWaveShape::O && hlcs[0].G == LvWaveShape::G && hlcs[1].G == LvWaveShape::G &&
-        hlcs[0].basis == BASIS_RBF && hlcs[1].basis == BASIS_RBF &&
-        (hlcs[0].norm == NORM_TANH_FAST || hlcs[0].norm == NORM_SOFTSIGN)) {
+    if (chain_is_lv_wave(hlcs, nl, B, wide)) {
         const size_t pre = 2 * sizeof(LayerConst) + sizeof(T) * (size_t)P * 10;   // ps, μ [2], kμ [7]
         size_t lds = pre + 2 * sizeof(double) * a.nsteps;
         const size_t rec = sizeof(T) * ((size_t)a.nsteps * 7 + 1) * LvWaveShape::I;
@@ -2234,5 +2274,6 @@ hipError_t launch_kd_chain_vjp_stage(const LayerConst* hlcs, int nl, const Layer
 KAN_COL_INST(double)
 KAN_COL_INST(float)
 #undef KAN_COL_INST
+#endif   // KAN_COL_DEVICE_ONLY
 
 }  // namespace kan

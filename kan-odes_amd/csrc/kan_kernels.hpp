@@ -96,6 +96,30 @@ struct AdamArgs {
     double c1, c2;         // 1 - βp (βp = β^t, Flux's running powers before this step advances them)
     double eps, eta;
 };
+// One entry of the step: the single statement of its arithmetic (adam_step_kernel and the fused training loop
+// kd_chain_train_lvsp_kernel both call it).  m, v <- the stored moments; returns the new x.  Every product, sum
+// and quotient is rounded on its own (round to nearest: what the __d*_rn intrinsics promise, the statement above and
+// kanode.Adam's): written as plain operators with contraction off, because the intrinsics are inline functions whose
+// own operators carry the translation unit's contraction mode -- the compiler fused some product-sum pairs into fma,
+// differently in each kernel this was inlined into, and the two kernels' steps then differed in the last bit.
+template <typename T>
+__device__ __forceinline__ T adam_entry(T x, T& m, T& v, T g, const AdamArgs& a) {
+#pragma clang fp contract(off)
+    const double d = (double)g * a.scale;
+    const double mt = a.beta1 * (double)m + a.omb1 * d;
+    const double vt = a.beta2 * (double)v + (a.omb2 * d) * d;
+    const T ms = (T)mt, vs = (T)vt;          // the stored moments (rounded for T = float)
+    m = ms;
+    v = vs;
+    const double den = ::sqrt((double)vs / a.c2) + a.eps;
+    const double step = (((double)ms / a.c1) / den) * a.eta;
+    if constexpr (sizeof(T) == 8) {
+        return (T)((double)x - step);
+    } else {
+        const float sf = (float)step;        // the step rounded to T before a subtraction in T
+        return (T)((float)x - sf);
+    }
+}
 template <typename T>
 hipError_t launch_adam_step(T* x, T* m, T* v, const T* g, int64_t n, const AdamArgs& a, hipStream_t st);
 
@@ -427,6 +451,57 @@ constexpr int kChainAdjointMaxSteps = 1024;   // forward steps held in LDS
 template <typename T>
 hipError_t launch_kd_chain_adjoint(const LayerConst* hlcs, int nl, const LayerConst* lcs, const T* p, int64_t P,
                                    int64_t B, const ChainAdjointArgs& a, hipStream_t st, bool wide);
+// K whole training iterations of one Lotka-Volterra trajectory in ONE launch (kd_chain_train_lvsp_kernel,
+// kan_col.hip; LV_driver_KANODE.jl:279-291): per iteration the forward solve at p_it (kd_chain_tsit5_kernel's
+// arithmetic, dense output kept on the device), loss[it] = mean((u_save - X)²) and its cotangent, the
+// InterpolatingAdjoint (kd_chain_adjoint_lvsp_kernel's body), the Adam step (adam_entry) and, with a test
+// problem, the solve over (t0, tf_test) at p_{it+1} for loss_test[it].  Covers exactly the shapes
+// launch_kd_chain_adjoint gives to kd_chain_adjoint_lvsp_kernel (chain_train_supported).
+enum ChainTrainStop {
+    kTrainOk = 0,
+    kTrainForwardMaxiters = 1,   // the forward solve reached maxiters
+    kTrainDenseCapacity = 2,     // more accepted forward steps than cap
+    kTrainAdjointMaxiters = 3,   // the adjoint reached maxiters
+    kTrainLossNotFinite = 4,
+    kTrainTestMaxiters = 5       // the test-loss solve reached maxiters (after the iteration's update)
+};
+struct ChainTrainArgs {
+    double t0, tf, dt, abstol, reltol, dtmin, beta1, beta2, gamma, qmin, qmax, qoldinit;   // solver options
+    int32_t adaptive, stage_rec;   // stage_rec: the dense output lives in LDS (else in rec)
+    int64_t maxiters, cap;         // cap: dense-output steps of one forward solve (<= kChainAdjointMaxSteps)
+    const double* u0;              // [2]
+    const double* saveat;          // [n_save] (device)
+    const double* target;          // [n_save][2]
+    int64_t n_save;
+    double dl_scale;               // 2 / (n_save·2)
+    const double* stops;           // the adjoint's jump groups (one_launch_adj_args' layout)
+    const int32_t* jrows;
+    const int32_t* joff;
+    int64_t nstops;
+    double tf_test;                // the test problem (n_save_test = 0: none)
+    const double* saveat_test;     // [n_save_test]
+    const double* target_test;     // [n_save_test][2]
+    int64_t n_save_test;
+    double eta, ab1, ab2, omb1, omb2, eps;   // Adam: η, β, 1 - β, ϵ
+    double bp1, bp2;               // the running powers βp on entry
+    int64_t n_iters;
+    double* p;                     // [P] in/out
+    double* m;                     // [P] in/out
+    double* v;                     // [P] in/out
+    double* rec;                   // [cap·7·2 + 2] dense output and k1_0 when !stage_rec (else unused)
+    double* loss;                  // [n_iters]
+    double* loss_test;             // [n_iters] or null
+    double* grad;                  // [n_iters][P] or null
+    double* p_before;              // [n_iters][P] or null
+    int64_t* counts;               // [n_iters][4] or null: forward naccept/nreject, adjoint naccept/nreject
+    int64_t* out;                  // iters_done, ChainTrainStop
+};
+bool chain_train_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B, size_t esize, bool wide);
+// the dynamic LDS of a launch with these sizes, and whether the dense output of `cap` steps is staged in it;
+// 0 when the problem does not fit at all
+size_t chain_train_lds(int64_t cap, int64_t n_save, int64_t n_save_test, int* stage_rec);
+hipError_t launch_kd_chain_train(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P,
+                                 const ChainTrainArgs& a, hipStream_t st);
 // A whole InterpolatingAdjoint step of a small chain per trajectory column (kd_chain_vjp_step_kernel, kan_col.hip):
 // the six adjoint stages of kanode_solve.cpp adjoint_t in one launch, λ and kλ_1..kλ_7 of a column in registers.
 // Stage s reads the forward dense output u_i + Σ_q su_c[s][q] k_{i,q} (K form, the forward step holding stage s)

@@ -48,14 +48,22 @@ __device__ __forceinline__ double onewg_bsum(double v, double* red) {
 }
 
 // The forward solve (solve_t): u0[n] -> u_save [n_save][n], the dense output and the counters in a.out.
-template <typename T, class Mdl>
+// WAVE: the whole problem lives on the calling wave (other waves of the block may do something else meanwhile):
+// the error norm is the wave sum alone (what onewg_bsum returns in a one-wave block, bit for bit: the other
+// waves' zeros change no bit of a sum of squares), no block barrier is executed, red is unused and the wave's
+// lane 0 writes the step records and counters.  a's pointers may then be LDS addresses.
+template <typename T, class Mdl, bool WAVE = false>
 __device__ __forceinline__ void onewg_tsit5(Mdl& m, const T* __restrict__ u0, const ChainSolveArgs& a, double* red) {
     using K = Tsit5Tab;
     const bool act = m.act;
     const int64_t idx = m.idx, n = m.n;
     T* __restrict__ usave = reinterpret_cast<T*>(a.u_save);
     T* __restrict__ rec = reinterpret_cast<T*>(a.rec);
-    auto bsum = [&](double v) -> double { return onewg_bsum(act ? v : 0.0, red); };
+    const bool lead = WAVE ? (threadIdx.x & (kWave - 1)) == 0 : threadIdx.x == 0;
+    auto bsum = [&](double v) -> double {
+        if constexpr (WAVE) return wave_sum(act ? v : 0.0);
+        else return onewg_bsum(act ? v : 0.0, red);
+    };
     T u = act ? u0[idx] : T(0);
     T k[7];
     k[0] = m.rhs(u);
@@ -140,7 +148,7 @@ __device__ __forceinline__ void onewg_tsit5(Mdl& m, const T* __restrict__ u0, co
 #pragma unroll
                 for (int q = 1; q < 7; ++q) r[(int64_t)q * n + idx] = k[q];
             }
-            if (threadIdx.x == 0) {
+            if (lead) {
                 a.ts[naccept] = t;
                 a.dts[naccept] = dt;
                 if (a.hts) {
@@ -156,7 +164,7 @@ __device__ __forceinline__ void onewg_tsit5(Mdl& m, const T* __restrict__ u0, co
         dt = dtnew;
     }
     if (status == 0 && it == a.maxiters && !(t >= tf - 1e-14 * ::fmax(1.0, ::fabs(tf)))) status = 1;
-    if (threadIdx.x == 0) {
+    if (lead) {
         if (a.hts) __threadfence_system();   // the host reads the step records once it sees the counters
         a.out[0] = naccept;
         a.out[1] = nreject;

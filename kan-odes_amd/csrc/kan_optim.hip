@@ -23,16 +23,11 @@ __global__ void __launch_bounds__(kBlock)
 adam_step_kernel(T* __restrict__ x, T* __restrict__ m, T* __restrict__ v, const T* __restrict__ g, int64_t n,
                  AdamArgs a) {
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const double d = __dmul_rn((double)g[i], a.scale);
-        const double mt = __dadd_rn(__dmul_rn(a.beta1, (double)m[i]), __dmul_rn(a.omb1, d));
-        const double vt = __dadd_rn(__dmul_rn(a.beta2, (double)v[i]), __dmul_rn(__dmul_rn(a.omb2, d), d));
-        const T ms = (T)mt, vs = (T)vt;          // the stored moments (rounded for T = float)
+        T ms = m[i], vs = v[i];
+        const T xn = adam_entry<T>(x[i], ms, vs, g[i], a);   // (kan_kernels.hpp: the one statement of the step)
         m[i] = ms;
         v[i] = vs;
-        const double den = __dadd_rn(::sqrt(__ddiv_rn((double)vs, a.c2)), a.eps);
-        const double step = __dmul_rn(__ddiv_rn(__ddiv_rn((double)ms, a.c1), den), a.eta);
-        if constexpr (std::is_same<T, double>::value) x[i] = __dsub_rn(x[i], step);
-        else x[i] = __fsub_rn(x[i], (float)step);
+        x[i] = xn;
     }
 }
 

@@ -90,6 +90,11 @@ struct kanode_handle {
     kan::GridOverride grid_ovr{};     // KANODE_OPT_GRID_{RHS,VJP,ADJ_STEP} (0 = default)
     // the integrator's storage for solves without a dense output (kanode_solve.cpp)
     kanode_solution* solve_cache = nullptr;
+    // the device-resident training loop (kanode_train_tsit5): result words | dense-output block | meta, and the
+    // meta bytes last uploaded
+    void* train_buf = nullptr;
+    size_t train_bytes = 0;
+    std::vector<char> train_meta;
     // table reuse inside one integrator solve (p constant): build each table set once
     bool hold_tables = false;
     bool built_phi = false, built_vjp = false;
@@ -1014,6 +1019,7 @@ void kanode_destroy(kanode_handle* h) {
     if (h->cstep_slab) (void)hipFree(h->cstep_slab);
     if (h->step_slab) (void)hipFree(h->step_slab);
     if (h->fin_ctr) (void)hipFree(h->fin_ctr);
+    if (h->train_buf) (void)hipFree(h->train_buf);
     if (h->solve_cache) kanode_solution_free(h->solve_cache);
     delete h;
 }
@@ -1680,6 +1686,74 @@ kanode_status kanode_internal_chain_adjoint(kanode_handle* h, const void* p, int
     if (e == hipErrorNotSupported) return KANODE_OK;
     if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_adjoint: ") + hipGetErrorString(e));
     launched = true;
+    return KANODE_OK;
+}
+bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch) {
+    return h->spec.rhs_kind == KANODE_RHS_CHAIN && kanode_internal_chain_tsit5_ok(h, batch) &&
+           kan::chain_train_supported(h->hlc, h->n_layers, h->P, batch, h->esize, h->chain_wide);
+}
+kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs* a, const std::vector<char>& meta,
+                                          int64_t res[2], void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    // the dense-output capacity of one forward solve: KANODE_OPT_FUSED_SOLVE_CAP, else the most steps whose dense
+    // output still fits in LDS next to the rest (at least 64: a smaller block stays in global memory instead)
+    int64_t cap = std::min<int64_t>(h->fused_solve_cap, kan::kChainAdjointMaxSteps);
+    if (cap < 1) {
+        int sr = 0;
+        int64_t lo = 0, hi = kan::kChainAdjointMaxSteps;   // the largest staged cap (lo stages, hi + 1 does not)
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) / 2;
+            if (kan::chain_train_lds(mid, a->n_save, a->n_save_test, &sr) && sr) lo = mid;
+            else hi = mid - 1;
+        }
+        cap = lo >= 64 ? lo : kan::kChainAdjointMaxSteps;
+    }
+    if (!a->adaptive && h->fused_solve_cap < 1) {   // fixed steps: exactly the steps of the solve (solve_fused_t's count)
+        int64_t n = 0;
+        for (double t = a->t0, dt = a->dt;
+             n < kan::kChainAdjointMaxSteps && !(t >= a->tf - 1e-14 * std::max(1.0, std::fabs(a->tf))); ++n) {
+            dt = std::min(dt, a->tf - t);
+            t = t + dt;
+        }
+        cap = std::max<int64_t>(n, 1);
+    }
+    int stage_rec = 0;
+    if (!kan::chain_train_lds(cap, a->n_save, a->n_save_test, &stage_rec))
+        return fail(h, KANODE_ERR_UNSUPPORTED, "kanode_train_tsit5: not supported (saveat lists too long for one workgroup's LDS)");
+    const size_t off_rec = 64;
+    const size_t off_meta = off_rec + sizeof(double) * ((size_t)kan::kChainAdjointMaxSteps * 7 * 2 + 2);
+    const size_t need = off_meta + meta.size() + 64;
+    if (h->train_bytes < need) {
+        HIP_TRY(h, hipStreamSynchronize(st));
+        if (h->train_buf) HIP_TRY(h, hipFree(h->train_buf));
+        h->train_buf = nullptr;
+        h->train_bytes = 0;
+        h->train_meta.clear();
+        HIP_TRY(h, hipMalloc(&h->train_buf, need));
+        h->train_bytes = need;
+    }
+    char* base = (char*)h->train_buf;
+    if (h->train_meta != meta) {
+        // (the earlier calls synchronised, so nothing on the device still reads the old bytes)
+        HIP_TRY(h, hipMemcpy(base + off_meta, meta.data(), meta.size(), hipMemcpyHostToDevice));
+        h->train_meta = meta;
+    }
+    const double* md = (const double*)(base + off_meta);
+    a->saveat = md;
+    a->saveat_test = md + a->n_save;
+    a->stops = md + a->n_save + a->n_save_test;
+    a->joff = (const int32_t*)(a->stops + a->nstops);
+    a->jrows = a->joff + a->nstops + 2;
+    a->cap = cap;
+    a->stage_rec = stage_rec;
+    a->rec = (double*)(base + off_rec);
+    a->out = (int64_t*)base;
+    const hipError_t e = kan::launch_kd_chain_train(h->hlc, h->n_layers, h->dlc, h->P, *a, st);
+    if (e == hipErrorNotSupported)
+        return fail(h, KANODE_ERR_UNSUPPORTED, "kanode_train_tsit5: not supported (shape not covered by the training kernel)");
+    if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_train: ") + hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(res, a->out, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
     return KANODE_OK;
 }
 bool kanode_internal_pair_persist_ok(const kanode_handle* h) {

@@ -14,6 +14,7 @@
 namespace kan {
 struct ChainSolveArgs;
 struct ChainAdjointArgs;
+struct ChainTrainArgs;
 struct AdjStepArgs;
 struct PairAdjArgs;
 struct FkLoopArgs;
@@ -110,6 +111,14 @@ kanode_status kanode_internal_fk_adjoint_step(kanode_handle* h, const void* p, k
                                               const AdjAdaptiveFinish* af = nullptr);
 kanode_status kanode_internal_chain_adjoint(kanode_handle* h, const void* p, int64_t batch,
                                             const kan::ChainAdjointArgs* a, void* stream, bool& launched);   // drop pending reductions (error paths)
+// the device-resident training loop (kd_chain_train_lvsp_kernel, kanode_train_tsit5): whether the handle takes it
+// at this batch, and one launch.  meta = saveat [n_save] | saveat_test [n_save_test] | stops [nstops] (doubles),
+// then joff [nstops + 2] | jrows (int32): kept on the handle (uploaded only when it differs from the last call's),
+// as are the dense-output block and the two result words; a's pointers to them, cap and stage_rec are set here.
+// Synchronises; res = iterations done, stop reason.
+bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch);
+kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs* a, const std::vector<char>& meta,
+                                          int64_t res[2], void* stream);
 // the persistent surrogate-pair adjoint (kd_pair_adjoint_kernel): whether the handle takes it
 // (KANODE_OPT_PAIR_PERSIST, fp64 surrogate pair), its workgroup count, and the launch (launched =
 // false when the kernel does not cover the shape / batch)

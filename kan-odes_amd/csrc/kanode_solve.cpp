@@ -1781,23 +1781,22 @@ kanode_status adjoint_t(kanode_handle* h, const void* p, kanode_solution* s, con
 // The stops, saveat jump groups and options of the one-launch adjoints (adjoint_t's semantics): the jump
 // groups and stops go to the solution's adj_meta buffer, everything else into a (rec, k1_0, ts, dts and
 // nsteps are the caller's).
-kanode_status one_launch_adj_args(kanode_handle* h, kanode_solution* s, const void* dl_du, void* du0, void* dp,
-                                  const kanode_solver_options& o, kan::ChainAdjointArgs& a, hipStream_t st) {
-    if (!o.adaptive && !(o.dt > 0))
-        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "fixed-step adjoint needs opt->dt > 0");
-    const double t0 = s->t0, tf = s->tf, TT = tf - t0;
+// (the groups depend on t0, tf and saveat alone, not on p: the training loop builds them once per launch)
+void adjoint_jump_groups(double t0, double tf, const std::vector<double>& saveat, bool have_dl,
+                         std::vector<double>& stops, std::vector<int32_t>& rows, std::vector<int32_t>& off) {
+    const double TT = tf - t0;
     const double eps = 1e-12 * std::max(1.0, std::fabs(tf));
     // the jump groups of adjoint_t: distinct saveat values and their dl_du rows
     struct Jump { double ts; std::vector<int32_t> rows; };
     std::vector<Jump> jumps;
-    for (int64_t jx = 0; jx < (int64_t)s->saveat.size(); ++jx) {
-        auto f = std::find_if(jumps.begin(), jumps.end(), [&](const Jump& x) { return x.ts == s->saveat[jx]; });
-        if (f == jumps.end()) jumps.push_back({s->saveat[jx], {(int32_t)jx}});
+    for (int64_t jx = 0; jx < (int64_t)saveat.size(); ++jx) {
+        auto f = std::find_if(jumps.begin(), jumps.end(), [&](const Jump& x) { return x.ts == saveat[jx]; });
+        if (f == jumps.end()) jumps.push_back({saveat[jx], {(int32_t)jx}});
         else f->rows.push_back((int32_t)jx);
     }
     std::vector<std::pair<double, int>> st_j;   // (τ of the stop, jump)
     std::vector<int32_t> init_rows, final_rows;
-    if (dl_du) {
+    if (have_dl) {
         for (int q = 0; q < (int)jumps.size(); ++q) {
             const Jump& jm = jumps[q];
             if (jm.ts == tf) init_rows.insert(init_rows.end(), jm.rows.begin(), jm.rows.end());
@@ -1806,8 +1805,9 @@ kanode_status one_launch_adj_args(kanode_handle* h, kanode_solution* s, const vo
         }
     }
     std::sort(st_j.begin(), st_j.end());
-    std::vector<double> stops;
-    std::vector<int32_t> rows(init_rows), off{0, (int32_t)init_rows.size()};
+    stops.clear();
+    rows = init_rows;
+    off = {0, (int32_t)init_rows.size()};
     for (auto& x : st_j) {
         stops.push_back(x.first);
         const Jump& jm = jumps[x.second];
@@ -1818,6 +1818,16 @@ kanode_status one_launch_adj_args(kanode_handle* h, kanode_solution* s, const vo
     stops.push_back(TT);
     rows.insert(rows.end(), final_rows.begin(), final_rows.end());
     off.push_back((int32_t)rows.size());
+}
+
+kanode_status one_launch_adj_args(kanode_handle* h, kanode_solution* s, const void* dl_du, void* du0, void* dp,
+                                  const kanode_solver_options& o, kan::ChainAdjointArgs& a, hipStream_t st) {
+    if (!o.adaptive && !(o.dt > 0))
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "fixed-step adjoint needs opt->dt > 0");
+    const double t0 = s->t0, tf = s->tf;
+    std::vector<double> stops;
+    std::vector<int32_t> rows, off;
+    adjoint_jump_groups(t0, tf, s->saveat, dl_du != nullptr, stops, rows, off);
     const int64_t ns = (int64_t)stops.size();
     // device copies: stops | joff | jrows
     const size_t bytes = ns * sizeof(double) + off.size() * sizeof(int32_t) + (rows.size() + 1) * sizeof(int32_t) + 64;
@@ -2241,6 +2251,118 @@ extern "C" kanode_status kanode_forward_sensitivity_tsit5(kanode_handle* h, cons
         stats->naccept = res[0];
         stats->nreject = res[1];
         stats->nf = res[2];
+    }
+    return KANODE_OK;
+}
+
+// ---- the device-resident training loop (kd_chain_train_lvsp_kernel) ---------------------------
+extern "C" int32_t kanode_train_supported(const kanode_handle* h, int64_t batch) {
+    return h && batch >= 1 && kanode_internal_chain_train_ok(h, batch) ? 1 : 0;
+}
+
+extern "C" kanode_status kanode_train_tsit5(kanode_handle* h, void* p, void* m, void* v, const void* u0, int64_t batch,
+                                            double t0, double tf, const double* saveat, int64_t n_save,
+                                            const void* target, double tf_test, const double* saveat_test,
+                                            int64_t n_save_test, const void* target_test,
+                                            const kanode_solver_options* opt, double eta, double beta1, double beta2,
+                                            double eps, double beta1_t, double beta2_t, int64_t n_iters, double* loss,
+                                            double* loss_test, void* grad, void* p_before, int64_t* counts,
+                                            int64_t* iters_done, int32_t* stop_reason, void* stream) {
+    SOLVE_TRY(kanode_internal_check(h));
+    if (iters_done) *iters_done = 0;
+    if (stop_reason) *stop_reason = KANODE_TRAIN_OK;
+    const kanode_solver_options o = resolved(opt);
+    SOLVE_TRY(check_opts(h, o));
+    if (batch < 1 || !kanode_internal_chain_train_ok(h, batch))
+        return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
+                                    "kanode_train_tsit5: not supported (covered: one trajectory of an fp64 chain [2,10,2], "
+                                    "G = 5, rbf, base activations, tanh_fast / softsign, fused_solve and chain_wide on)");
+    if (!p || !m || !v || !u0 || !target || !loss || !saveat || n_save < 1 || n_iters < 1 || !(tf > t0) || !iters_done ||
+        !stop_reason)
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "kanode_train_tsit5: null pointer, n_save < 1, n_iters < 1 or tf <= t0");
+    if (n_save_test < 0 || (n_save_test > 0 && (!saveat_test || !target_test || !loss_test || !(tf_test > t0))))
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "kanode_train_tsit5: test problem needs saveat_test, target_test, loss_test and tf_test > t0");
+    // 1 - β^t must stay positive: the bias corrections divide by it (kanode_adam_step's condition)
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && beta1_t < 1.0 && beta2_t < 1.0))
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "kanode_train_tsit5: Adam needs 0 <= beta < 1 and beta_t < 1");
+    auto check_saveat = [&](const double* sv, int64_t n, double te) -> bool {
+        for (int64_t j = 1; j < n; ++j)
+            if (!(sv[j] >= sv[j - 1])) return false;
+        return n == 0 || (sv[0] >= t0 - 1e-12 * std::max(1.0, std::fabs(t0)) && sv[n - 1] <= te + 1e-12 * std::max(1.0, std::fabs(te)));
+    };
+    if (!check_saveat(saveat, n_save, tf) || !check_saveat(saveat_test, n_save_test, tf_test))
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "kanode_train_tsit5: saveat must ascend within [t0, tf]");
+    hipStream_t st = (hipStream_t)stream;
+    if (capturing(st)) return kanode_internal_fail(h, KANODE_ERR_CAPTURE, "kanode_train_tsit5 reads its status words");
+    // the adjoint's stops and jump groups (those of kanode_adjoint_tsit5 for this saveat)
+    std::vector<double> stops;
+    std::vector<int32_t> rows, off;
+    adjoint_jump_groups(t0, tf, std::vector<double>(saveat, saveat + n_save), true, stops, rows, off);
+    const int64_t ns = (int64_t)stops.size();
+    std::vector<char> meta((size_t)(n_save + n_save_test + ns) * sizeof(double) + (off.size() + rows.size()) * sizeof(int32_t));
+    {
+        char* w = meta.data();
+        auto put = [&](const void* src, size_t bytes) {
+            if (bytes) std::memcpy(w, src, bytes);
+            w += bytes;
+        };
+        put(saveat, (size_t)n_save * sizeof(double));
+        put(saveat_test, (size_t)n_save_test * sizeof(double));
+        put(stops.data(), (size_t)ns * sizeof(double));
+        put(off.data(), off.size() * sizeof(int32_t));
+        put(rows.data(), rows.size() * sizeof(int32_t));
+    }
+    kan::ChainTrainArgs a{};
+    a.t0 = t0;
+    a.tf = tf;
+    a.dt = o.dt;
+    a.abstol = o.abstol;
+    a.reltol = o.reltol;
+    a.dtmin = o.dtmin;
+    a.beta1 = o.beta1;
+    a.beta2 = o.beta2;
+    a.gamma = o.gamma;
+    a.qmin = o.qmin;
+    a.qmax = o.qmax;
+    a.qoldinit = o.qoldinit;
+    a.adaptive = o.adaptive ? 1 : 0;
+    a.maxiters = o.maxiters;
+    a.u0 = (const double*)u0;
+    a.target = (const double*)target;
+    a.n_save = n_save;
+    a.dl_scale = 2.0 / (double)(n_save * kanode_internal_state_length(h) * batch);
+    a.nstops = ns;
+    a.tf_test = tf_test;
+    a.target_test = (const double*)target_test;
+    a.n_save_test = n_save_test;
+    a.eta = eta;
+    a.ab1 = beta1;
+    a.ab2 = beta2;
+    a.omb1 = 1.0 - beta1;
+    a.omb2 = 1.0 - beta2;
+    a.eps = eps;
+    a.bp1 = beta1_t;
+    a.bp2 = beta2_t;
+    a.n_iters = n_iters;
+    a.p = (double*)p;
+    a.m = (double*)m;
+    a.v = (double*)v;
+    a.loss = loss;
+    a.loss_test = n_save_test > 0 ? loss_test : nullptr;
+    a.grad = (double*)grad;
+    a.p_before = (double*)p_before;
+    a.counts = counts;
+    int64_t res[2] = {0, 0};
+    SOLVE_TRY(kanode_internal_chain_train(h, &a, meta, res, st));
+    *iters_done = res[0];
+    *stop_reason = (int32_t)res[1];
+    if (res[1] != KANODE_TRAIN_OK) {
+        static const char* const why[] = {"", "forward Tsit5: maxiters reached", "forward dense-output capacity exceeded "
+                                          "(KANODE_OPT_FUSED_SOLVE_CAP)", "adjoint Tsit5: maxiters reached",
+                                          "loss is not finite", "test-loss Tsit5: maxiters reached"};
+        const int64_t r = res[1] >= 1 && res[1] <= 5 ? res[1] : 0;
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "kanode_train_tsit5: stopped at iteration " +
+                                                                   std::to_string(res[0]) + ": " + why[r]);
     }
     return KANODE_OK;
 }

@@ -100,6 +100,8 @@ OPT_CHAIN_WIDE = 17
 OPT_RECORD_ADJOINT_STEPS = 18
 OPT_FK_DEVICE_LOOP = 19
 ADJ_NONE, ADJ_HOST_LOOP, ADJ_CHAIN_WG, ADJ_PAIR_PERSIST, ADJ_PAIR_FALLBACK = 0, 1, 2, 3, 4   # kanode_adjoint_path
+TRAIN_STOP = {0: "ok", 1: "forward_maxiters", 2: "dense_capacity", 3: "adjoint_maxiters", 4: "loss_not_finite",
+              5: "test_maxiters"}   # kanode_train_stop
 OPTIONS = {"pointwise_table": OPT_POINTWISE_TABLE, "fused_step": OPT_FUSED_STEP, "fused_solve": OPT_FUSED_SOLVE,
            "fused_solve_cap": OPT_FUSED_SOLVE_CAP, "grid_rhs": OPT_GRID_RHS, "grid_vjp": OPT_GRID_VJP,
            "grid_adj_step": OPT_GRID_ADJ_STEP, "adj_step_rows": OPT_ADJ_STEP_ROWS, "pair_vjp": OPT_PAIR_VJP,
@@ -149,6 +151,12 @@ SIGNATURES = [
     ("kanode_edge_activations", C.c_int, [_H, C.c_int32, _P, _P, _P, C.c_int64, _P]),
     ("kanode_adam_step", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double,
                                    C.c_double, C.c_double, C.c_double, C.c_double, _P]),
+    ("kanode_train_supported", C.c_int32, [_H, C.c_int64]),
+    ("kanode_train_tsit5", C.c_int, [_H, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double),
+                                     C.c_int64, _P, C.c_double, C.POINTER(C.c_double), C.c_int64, _P,
+                                     C.POINTER(SolverOptsC), C.c_double, C.c_double, C.c_double, C.c_double,
+                                     C.c_double, C.c_double, C.c_int64, _P, _P, _P, _P, _P,
+                                     C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P]),
     ("kanode_comm_unique_id", C.c_int, [_P]),
     ("kanode_comm_create", C.c_int, [C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(_P)]),
     ("kanode_comm_allreduce_sum", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),

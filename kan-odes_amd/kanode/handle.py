@@ -379,6 +379,52 @@ class KanodeHandle:
                 self._h, "kanode_adjoint_tsit5")
         return du0, dp, dict(naccept=st.naccept, nreject=st.nreject, nf=st.nf)
 
+    def train_supported(self, batch: int) -> bool:
+        """kanode_train_supported: the device-resident training loop covers this handle at `batch` trajectories."""
+        return bool(L.lib().kanode_train_supported(self._h, int(batch)))
+
+    def train_tsit5(self, p, m, v, u0, t0: float, tf: float, saveat, target, opts: "L.SolverOptsC", eta: float,
+                    beta, eps: float, beta_t, n_iters: int, test=None, record: bool = False):
+        """n_iters whole training iterations in one launch (kanode_train_tsit5): p, m, v are updated in place.
+        test: None or (tf_test, saveat_test, target_test).  Returns a dict: loss (n_iters,), loss_test (n_iters,)
+        or None, with record grad / p_before (n_iters, P) and counts (n_iters, 4), and iters_done, stop (a
+        _lib.TRAIN_STOP name), error (the library's message when the loop stopped early, else None).  loss[it] is
+        the loss at p_it, before the update; loss_test[it] at p_{it+1}.  An unsupported shape or a bad argument
+        raises KanodeError; a stopped loop does not (the caller reads iters_done)."""
+        B = u0.shape[0] if u0.dim() == 2 else 1
+        for t, nm in ((p, "p"), (m, "m"), (v, "v")):
+            self._check_t(t, (self.P,), nm)
+        self._check_t(u0, None, "u0")
+        if u0.numel() != B * self.N:
+            raise ValueError("train_tsit5 needs u0 of B x N entries")
+        self._check_t(target, (len(saveat),) + tuple(u0.shape), "target")
+        n = int(n_iters)
+        kw = dict(dtype=torch.float64, device=self.device)
+        loss = torch.zeros(n, **kw)
+        tf_t, sv_t, n_t, tg_t, loss_t = 0.0, None, 0, None, None
+        if test is not None:
+            tf_t, sat, tg_t = test
+            self._check_t(tg_t, (len(sat),) + tuple(u0.shape), "target_test")
+            sv_t, n_t = self._saveat_c(sat), len(sat)
+            loss_t = torch.zeros(n, **kw)
+        grad = torch.zeros((n, self.P), **kw) if record else None
+        pb = torch.zeros((n, self.P), **kw) if record else None
+        counts = torch.zeros((n, 4), dtype=torch.int64, device=self.device) if record else None
+        done, stop = C.c_int64(0), C.c_int32(0)
+        st = L.lib().kanode_train_tsit5(self._h, _ptr(p), _ptr(m), _ptr(v), _ptr(u0), B, float(t0), float(tf),
+                                        self._saveat_c(saveat), len(saveat), _ptr(target), float(tf_t), sv_t, n_t,
+                                        _ptr(tg_t), C.byref(opts), float(eta), float(beta[0]), float(beta[1]),
+                                        float(eps), float(beta_t[0]), float(beta_t[1]), n, _ptr(loss), _ptr(loss_t),
+                                        _ptr(grad), _ptr(pb), _ptr(counts), C.byref(done), C.byref(stop),
+                                        _stream(self.device))
+        err = None
+        if st != L.OK:
+            if stop.value == 0:
+                L.check(st, self._h, "kanode_train_tsit5")
+            err = L.lib().kanode_last_error(self._h).decode()
+        return dict(loss=loss, loss_test=loss_t, grad=grad, p_before=pb, counts=counts, iters_done=int(done.value),
+                    stop=L.TRAIN_STOP.get(int(stop.value), str(stop.value)), error=err)
+
     def table_rejections(self):
         """Intervals the last table builds rejected: (φ, φ', swish), -1 for a table not built yet
         (kanode_table_rejections; their points take the direct formula)."""

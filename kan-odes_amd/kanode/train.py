@@ -232,7 +232,12 @@ class Trainer:
         return loss.detach(), g.detach(), sol
 
     def step(self) -> float:
-        loss, g, _ = self.loss_and_grad()
+        return self._step()[0]
+
+    def _step(self):
+        """One iteration: (loss, this rank's gradient, the forward Solution)."""
+        loss, g, sol = self.loss_and_grad()
+        g_own = g
         if self.tp:
             loss = torch.as_tensor(self.rhs.reduce_sum(float(loss)), dtype=g.dtype)
         scale = 1.0
@@ -250,4 +255,114 @@ class Trainer:
         self._pver += 1
         lv = float(loss)
         self.history.append(lv)
-        return lv
+        return lv, g_own, sol
+
+    def _native_run_ok(self) -> bool:
+        """Whether run() takes the device-resident loop (kanode_train_tsit5): the handle covers the shape, the
+        gradient is the plain-MSE InterpolatingAdjoint of this rank alone, and the optimiser is FusedAdam."""
+        hd = getattr(self.rhs, "hd", None)
+        if (hd is None or self.sensealg != "interpolating_adjoint" or self.group is not None or self.tp
+                or self.sparse_reg or type(self.opt) is not FusedAdam or not self.p.is_cuda):
+            return False
+        if self.p.dtype != torch.float64 or not (self.p.is_contiguous() and self.u0.is_contiguous()):
+            return False
+        if self.solver.control != "auto" or self.solver.replay_dts is not None \
+                or self.solver.replay_adjoint_dts is not None:
+            return False                                  # (host / hipGraph step control, replayed steps: step())
+        B = self.u0.shape[0] if self.u0.dim() == 2 else 1
+        return self._fast_path()[1] == "interpolating_adjoint" and hd.train_supported(B)
+
+    def run(self, n_iters: int, test=None, chunk: int = 256, record: bool = False) -> dict:
+        """n_iters iterations of the driver loop (LV_driver_KANODE.jl:279-291): step(), and with
+        test = (tspan_test, saveat_test, target_test) the test loss at the updated parameters after each.
+        Returns {"loss": [n_iters] (loss[it] at p_it, before the update, as step() returns it), "loss_test":
+        [n_iters] or None (loss_test[it] at p_{it+1})}, float64 CPU tensors; with record=True also "grad",
+        "p_before" ([n_iters, P], on p's device) and "counts" ([n_iters, 4] int64, CPU: forward naccept, nreject,
+        adjoint naccept, nreject).
+
+        Where the handle covers it (one Lotka-Volterra trajectory, fp64, plain MSE, FusedAdam, no group) the
+        iterations run on the device, at most `chunk` per kernel launch (no single kernel runs for long on a shared
+        machine): the optimiser's own m, v and running powers are used and advanced.  If the device loop stops (a
+        solve at maxiters, the dense-output capacity, a non-finite loss) the iterations before it are kept in
+        history and a KanodeError names the iteration and reason, p, m, v as the last good iteration left them.
+        Everything else is a plain loop of step() plus the test solve, on the CPU too.  The cached forward of
+        eval_loss is dropped either way."""
+        n_iters = int(n_iters)
+        if n_iters < 0 or chunk < 1:
+            raise ValueError("run: n_iters >= 0 and chunk >= 1")
+        if test is not None:
+            tspan_t, saveat_t, target_t = test
+            sv_t = _saveat_list(tspan_t, saveat_t)
+            sv_t = [s for s in sv_t if s <= float(tspan_t[1]) + 1e-12 * max(1.0, abs(float(tspan_t[1])))]
+        if n_iters > 0 and self._native_run_ok() and (
+                test is None or (float(tspan_t[0]) == float(self.tspan[0])
+                                 and tuple(target_t.shape) == (len(sv_t),) + tuple(self.u0.shape))):
+            return self._run_native(n_iters, None if test is None else (float(tspan_t[1]), sv_t, target_t),
+                                    int(chunk), record)
+        loss, loss_t, grads, pbs, counts = [], [], [], [], []
+        for _ in range(n_iters):
+            if record:
+                pbs.append(self.p.detach().clone())
+            lv, g, sol = self._step()
+            loss.append(lv)
+            if record:
+                grads.append(g.detach().clone().reshape(-1))
+                adj = sol.stats.get("adjoint", {})
+                counts.append([sol.stats.get("naccept", 0), sol.stats.get("nreject", 0), adj.get("naccept", 0),
+                               adj.get("nreject", 0)])
+            if test is not None:
+                with torch.no_grad():
+                    loss_t.append(float(mse_loss(solve(self.rhs, self.u0, tspan_t, self.p.detach(), saveat_t,
+                                                       self.solver).u, target_t)))
+        self._drop_pre()
+        out = {"loss": torch.tensor(loss, dtype=torch.float64),
+               "loss_test": torch.tensor(loss_t, dtype=torch.float64) if test is not None else None}
+        if record:
+            P = self.p.numel()
+            out["grad"] = torch.stack(grads) if grads else self.p.new_zeros((0, P))
+            out["p_before"] = torch.stack(pbs).reshape(len(pbs), P) if pbs else self.p.new_zeros((0, P))
+            out["counts"] = torch.tensor(counts, dtype=torch.int64).reshape(len(counts), 4)
+        return out
+
+    def _run_native(self, n_iters: int, test, chunk: int, record: bool) -> dict:
+        from . import _lib as L
+        hd = self.rhs.hd
+        self._drop_pre()
+        sv, _ = self._fast_path()
+        b1, b2 = self.opt.beta
+        st = self.opt.state.get(id(self.p))
+        if st is None:                                    # as FusedAdam.update creates them
+            st = [torch.zeros_like(self.p), torch.zeros_like(self.p), [b1, b2]]
+            self.opt.state[id(self.p)] = st
+        mt, vt, bp = st
+        oc = self.solver.to_c()
+        target = self.target.contiguous()
+        if test is not None:
+            test = (test[0], test[1], test[2].contiguous())
+        parts, left, err = [], n_iters, None
+        while left > 0 and err is None:
+            k = min(left, chunk)
+            r = hd.train_tsit5(self.p, mt, vt, self.u0, float(self.tspan[0]), float(self.tspan[1]), sv, target, oc,
+                               self.opt.eta, (b1, b2), self.opt.eps, bp, k, test=test, record=record)
+            d = r["iters_done"]
+            for _ in range(d):                            # Flux's βp .*= β, once per iteration done
+                bp[0] *= b1
+                bp[1] *= b2
+            self._pver += d
+            self.history.extend(r["loss"][:d].tolist())
+            parts.append((r, d))
+            left -= k
+            if r["error"] is not None:
+                err = (n_iters - left - k + d, r["stop"], r["error"])
+        self._drop_pre()
+        if err is not None:
+            raise L.KanodeError(f"Trainer.run: stopped at iteration {err[0]} ({err[1]}): {err[2]}; "
+                                f"p, m, v are those after {err[0]} iterations")
+
+        def cat(key, cpu):
+            t = torch.cat([r[key][:d] for r, d in parts])
+            return t.cpu() if cpu else t
+        out = {"loss": cat("loss", True), "loss_test": cat("loss_test", True) if test is not None else None}
+        if record:
+            out["grad"], out["p_before"], out["counts"] = cat("grad", False), cat("p_before", False), cat("counts", True)
+        return out
