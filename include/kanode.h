@@ -206,6 +206,12 @@ kanode_status kanode_reserve(kanode_handle* h, int64_t max_batch);
  *     The host queues launches ahead and never waits on a step.  0 = the host loops (one norm read per
  *     step).  Same controller arithmetic; the device sums the terms in another order and its pow may round
  *     differently, so step sizes agree to rounding, not bitwise.
+ *   KANODE_OPT_FSENS_WIDE (default 0): which fields kanode_forward_sensitivity_tsit5 covers.  0 = nx·batch
+ *     <= 64 (one state entry per lane).  1 = also 64 < nx·batch <= 128, by the same kernel with two entries
+ *     per lane (lane l carries entries l and l + 64; per entry the same arithmetic); fields of up to 64
+ *     entries still take the one-entry kernel.  2 (tests) = the two-entry kernel for every nx·batch <= 128:
+ *     with an empty upper half it returns the one-entry kernel's bits.  Any other value is INVALID_ARG.
+ *     kanode_forward_sensitivity_supported follows the option.
  * Options are read when a call is issued (never from the environment).  kanode_get_option
  * returns the current value, or -1 for an unknown option. */
 typedef enum {
@@ -227,7 +233,8 @@ typedef enum {
     KANODE_OPT_LAST_ADJOINT = 16,
     KANODE_OPT_CHAIN_WIDE = 17,
     KANODE_OPT_RECORD_ADJOINT_STEPS = 18,
-    KANODE_OPT_FK_DEVICE_LOOP = 19
+    KANODE_OPT_FK_DEVICE_LOOP = 19,
+    KANODE_OPT_FSENS_WIDE = 20
 } kanode_option;
 typedef enum {
     KANODE_ADJ_NONE = 0,            /* no adjoint on this handle yet */
@@ -370,7 +377,7 @@ kanode_status kanode_adjoint_tsit5(kanode_handle* h, const void* p, const kanode
  *     u_save[n_save, N, B] <- u(saveat[j]);  s_save[n_save, P, N, B] <- ∂u(saveat[j])/∂p   (device, either nullable)
  * so dL/dp = Σ_j Σ_i ∂L/∂u_i(t_j) · s_save[j, :, i] (the host's contraction, as the Dual pullback's).  Covered: the
  * pointwise + periodic Laplacian RHS (fp64, rbf, G = 5 or 10, base activation, softsign / tanh_fast) with
- * nx·batch <= 64, as ONE workgroup (control is ignored); KANODE_ERR_UNSUPPORTED otherwise.  Synchronous (reads the
+ * nx·batch <= 64 (<= 128 with KANODE_OPT_FSENS_WIDE), as ONE workgroup (control is ignored); KANODE_ERR_UNSUPPORTED otherwise.  Synchronous (reads the
  * step counters). */
 kanode_status kanode_forward_sensitivity_tsit5(kanode_handle* h, const void* p, const void* u0, int64_t batch,
                                                double t0, double tf, const double* saveat, int64_t n_save,

@@ -389,6 +389,10 @@ function fsens!(h::Handle, p::Ptr{Cvoid}, u0::Ptr{Cvoid}, B::Integer, tspan, sav
 end
 fsens_supported(h::Handle, B::Integer) = ccall(sym(:kanode_forward_sensitivity_supported), Int32,
                                                (Ptr{Cvoid}, Int64), h.ptr, B) == 1
+# KANODE_OPT_FSENS_WIDE (include/kanode.h): 1 = fields of 65 to 128 entries are covered too (two entries per lane)
+const OPT_FSENS_WIDE = Int32(20)
+fsens_wide!(h::Handle, v::Integer = 1) = check(h, ccall(sym(:kanode_set_option), Cint, (Ptr{Cvoid}, Int32, Int64),
+                                                        h.ptr, OPT_FSENS_WIDE, v))
 
 """solve_tsit5_fwd(h, u0, tspan, p, saveat; abstol, reltol) -> Array(sol), like solve_tsit5, but differentiable in p
 by forward sensitivities (ForwardDiffSensitivity, the reference's automatic choice for its small source-term
@@ -405,6 +409,7 @@ function fwd_impl(h::Handle, u0::AbstractVecOrMat, tspan, p::AbstractVector, sav
     ts = Vector{Float64}(saveat)
     issorted(ts) || throw(ArgumentError("saveat must be ascending"))
     B = size(u0, 2)
+    fsens_supported(h, B) || fsens_wide!(h)     # (idempotent: the whole range SciMLSensitivity's rule selects)
     fsens_supported(h, B) || throw(ArgumentError("forward sensitivities: not covered for this handle / batch"))
     pd, ud = upload(tohost(T, p)), upload(tohost(T, u0))
     out = Array{T}(undef, h.nin, B, length(ts))

@@ -165,7 +165,13 @@ fk_small_adjoint_kernel(const LayerConst* __restrict__ lcp, const double* __rest
 // LDS round per step) and the error norm's block sum.  TAB: φ, φ' and swish from the
 // piecewise-polynomial tables (PP_PHI, PP_DPHI, PP_SWISH staged in LDS, the reference formula off the table);
 // otherwise the reference formula throughout (odd Nx, table path off).
-template <int NORM, int GT, bool TAB>
+//
+// E: state entries per lane.  E = 1 is the layout above.  E = 2 (64 < Nx·B <= 128): lane l carries entries l and
+// l + 64, every per-entry statement is the one above written once per entry, and the LDS rows (the exchange and the
+// two slots) are 128 columns.  A stencil neighbour e' lives in lane e' & 63, half e' >> 6: a trajectory may straddle
+// entry 64, and its periodic wrap may cross the halves.  A lane gives lo + hi to the block sums, so with an empty
+// upper half (Nx·B <= 64) every sum has the bits of E = 1.
+template <int NORM, int GT, bool TAB, int E>
 __global__ void __launch_bounds__((GT + 2) * kWave)
 fk_small_fsens_kernel(const LayerConst* __restrict__ lcp, const double* __restrict__ p,
                       const double2* __restrict__ tables, FkSmallArgs s, const double* __restrict__ u0, int64_t B,
@@ -178,7 +184,8 @@ fk_small_fsens_kernel(const LayerConst* __restrict__ lcp, const double* __restri
         const int fns[3] = {PP_PHI, PP_DPHI, PP_SWISH};
         stage_tables(tl, tables, s.ni, fns, 3);
     }
-    double* __restrict__ xv = reinterpret_cast<double*>(tl + 3 * tsz);   // [waves][64] per-entry exchange
+    constexpr int W = E * kWave;                                         // entries per LDS row
+    double* __restrict__ xv = reinterpret_cast<double*>(tl + 3 * tsz);   // [waves][W] per-entry exchange
     KAN_EXP_TABLE_LDS(tab);   // (its barrier also publishes the tables)
     const Math<double> M{tab};
     const LayerConst& lc = *lcp;
@@ -187,17 +194,54 @@ fk_small_fsens_kernel(const LayerConst* __restrict__ lcp, const double* __restri
     const int nw = (int)(blockDim.x / kWave);
     const int Nx = s.Nx;
     const int64_t n = (int64_t)Nx * B;
-    const bool act = l < n;
-    const int j = l % Nx, b0 = l - j;
-    const int jm = act ? b0 + (j + Nx - 1) % Nx : l, jp = act ? b0 + (j + 1) % Nx : l;
+    // entry h of this lane: e[h] = l + 64 h, point j[h] of its trajectory, neighbours jm[h] / jp[h] (entry indices;
+    // an inactive entry points at itself)
+    bool act[E];
+    int e[E], j[E], jm[E], jp[E];
+#pragma unroll
+    for (int h = 0; h < E; ++h) {
+        e[h] = l + h * kWave;
+        act[h] = e[h] < n;
+        j[h] = e[h] % Nx;
+        const int b0 = e[h] - j[h];
+        jm[h] = act[h] ? b0 + (j[h] + Nx - 1) % Nx : e[h];
+        jp[h] = act[h] ? b0 + (j[h] + 1) % Nx : e[h];
+    }
     const bool sens = w > 0;   // (wave-uniform)
     const int kq = w - 1;
     const double2* tphi = tl;
     const double2* tdphi = tl + tsz;
     const double2* tsw = tl + 2 * tsz;
-    auto lap = [&](double v) -> double {
-        const double um = __shfl(v, jm, kWave), up = __shfl(v, jp, kWave);
-        return lap3<double>(um, v, up, j, Nx, s.cd, s.co);
+    // v at entry q of this wave (lane q & 63, half q >> 6)
+    auto at = [&](const double (&v)[E], int q) -> double {
+        if constexpr (E == 1) {
+            return __shfl(v[0], q, kWave);
+        } else {
+            const double lo = __shfl(v[0], q & (kWave - 1), kWave), hi = __shfl(v[1], q & (kWave - 1), kWave);
+            return q >= kWave ? hi : lo;
+        }
+    };
+    // E = 2: the four neighbour entries (7 bits each) and the first / last-point flags of both entries in one
+    // register, unpacked where they are used (what is derived from them is loop-invariant, and kept unpacked
+    // across the step loop it costs the registers this kernel does not have)
+    unsigned nbr = 0;
+    if constexpr (E > 1) {
+#pragma unroll
+        for (int h = 0; h < E; ++h)
+            nbr |= (unsigned)(jm[h] | (jp[h] << 7)) << (14 * h) | (unsigned)(j[h] == 0) << (28 + 2 * h) |
+                   (unsigned)(j[h] == Nx - 1) << (29 + 2 * h);
+    }
+    auto lap = [&](const double (&v)[E], int h) -> double {
+        if constexpr (E == 1) {
+            const double um = at(v, jm[h]), up = at(v, jp[h]);
+            return lap3<double>(um, v[h], up, j[h], Nx, s.cd, s.co);
+        } else {
+            unsigned pk = nbr;
+            asm volatile("" : "+v"(pk));   // (opaque here: nothing unpacked is hoisted out of the step loop)
+            const double um = at(v, (int)(pk >> (14 * h)) & 127), up = at(v, (int)(pk >> (14 * h + 7)) & 127);
+            const int i = (pk >> (28 + 2 * h)) & 1 ? 0 : ((pk >> (29 + 2 * h)) & 1 ? Nx - 1 : 1);   // (Nx >= 3)
+            return lap3<double>(um, v[h], up, i, Nx, s.cd, s.co);
+        }
     };
     // One evaluation of the Dual RHS at the stage input z (wave 0: the values y; wave 1 + k: the partial s_k):
     //   wave 0:      f(y) = (D lap y) + φ(y)                    (FkSmallModel::rhs), and the quantities every
@@ -205,66 +249,100 @@ fk_small_fsens_kernel(const LayerConst* __restrict__ lcp, const double* __restri
     //   wave 1 + k:  ((D lap) s_k + s_k φ'(y)) + ∂φ/∂p_k(y),  ∂φ/∂C_k = B_k(N(y)) by the reference formula,
     //                ∂φ/∂W = swish(y), read from that slot after the block barrier.
     // Only wave 0 evaluates at the values, so a partial wave costs a stencil, one fma and one exponential.
-    double* __restrict__ shv = xv + kFsensMaxWaves * kWave;   // [2][3][64]: φ', swish, N by slot
-    auto F = [&](double z, int slot) -> double {
-        double r = 0.0;
-        double* sh = shv + slot * 3 * kWave;
+    // [2][3][W]: φ', swish, N by slot (E = 2: after the exchange rows of this block's G + 2 waves)
+    double* __restrict__ shv = xv + (E == 1 ? kFsensMaxWaves : GT + 2) * W;
+    auto F = [&](const double (&z)[E], int slot, double (&r)[E]) {
+        double* sh = shv + slot * 3 * W;
         if (!sens) {
-            const double lp = lap(z);
-            double k = 0.0, dphi = 0.0, sw = 0.0;
-            bool ok = false, ok2 = false;
-            if constexpr (TAB) {
-                k = pp_eval(tphi, s.ni, s.inv_w, s.x0, z, ok);
-                ok2 = pp_eval2<true>(tdphi, tsw, s.ni, s.inv_w, s.x0, z, dphi, sw);
+#pragma unroll
+            for (int h = 0; h < E; ++h) {
+                const double lp = lap(z, h);
+                double k = 0.0, dphi = 0.0, sw = 0.0;
+                bool ok = false, ok2 = false;
+                if constexpr (TAB) {
+                    k = pp_eval(tphi, s.ni, s.inv_w, s.x0, z[h], ok);
+                    ok2 = pp_eval2<true>(tdphi, tsw, s.ni, s.inv_w, s.x0, z[h], dphi, sw);
+                }
+                if (!ok) {
+                    double sc;
+                    k = pp_direct<NORM, BASIS_RBF>(M, lc, p, lc.grid, z[h], sc);
+                }
+                if (!ok2) pp_direct_dphi_sw<NORM, BASIS_RBF>(M, lc, p, z[h], dphi, sw);
+                r[h] = lp + k;
+                sh[e[h]] = dphi;
+                sh[W + e[h]] = sw;
+                sh[2 * W + e[h]] = normalize<NORM, double>(M, lc.norm, z[h]);
+                if constexpr (E > 1) __builtin_amdgcn_sched_barrier(0);   // (one entry's evaluation at a time: registers)
             }
-            if (!ok) {
-                double sc;
-                k = pp_direct<NORM, BASIS_RBF>(M, lc, p, lc.grid, z, sc);
-            }
-            if (!ok2) pp_direct_dphi_sw<NORM, BASIS_RBF>(M, lc, p, z, dphi, sw);
-            r = lp + k;
-            sh[l] = dphi;
-            sh[kWave + l] = sw;
-            sh[2 * kWave + l] = normalize<NORM, double>(M, lc.norm, z);
         }
         __syncthreads();
         if (sens) {
-            const double lp = lap(z);
-            const double dphi = sh[l];
-            double dp = sh[kWave + l];
-            if (kq < GT) {
-                const double y = (sh[2 * kWave + l] - (double)lc.grid[kq]) * (double)lc.invh;
-                double aux;
-                dp = basis_direct<double>(M, BASIS_RBF, y, aux);
+#pragma unroll
+            for (int h = 0; h < E; ++h) {
+                const double lp = lap(z, h);
+                const double dphi = sh[e[h]];
+                double dp = sh[W + e[h]];
+                if (kq < GT) {
+                    const double y = (sh[2 * W + e[h]] - (double)lc.grid[kq]) * (double)lc.invh;
+                    double aux;
+                    dp = basis_direct<double>(M, BASIS_RBF, y, aux);
+                }
+                r[h] = (lp + z[h] * dphi) + dp;
+                if constexpr (E > 1) __builtin_amdgcn_sched_barrier(0);
             }
-            r = (lp + z * dphi) + dp;
         }
-        return r;
     };
-    // Σ over the waves of v at this lane's entry (value first, then the partials in order: the entry's Dual
-    // sse), the same total in every wave
-    auto pt_sum = [&](double v) -> double {
-        xv[w * kWave + l] = v;
+    // Σ over the waves of v at each of this lane's entries (value first, then the partials in order: the entry's
+    // Dual sse), the same totals in every wave; v of an inactive entry counts as zero
+    auto pt_sum = [&](const double (&v)[E], double (&t)[E]) {
+#pragma unroll
+        for (int h = 0; h < E; ++h) xv[w * W + e[h]] = act[h] ? v[h] : 0.0;
         __syncthreads();
-        double t = xv[l];
-        for (int q = 1; q < nw; ++q) t += xv[q * kWave + l];
+#pragma unroll
+        for (int h = 0; h < E; ++h) {
+            t[h] = xv[e[h]];
+            for (int q = 1; q < nw; ++q) t[h] += xv[q * W + e[h]];
+        }
         __syncthreads();
-        return t;
     };
-    auto bsum = [&](double v) -> double { return onewg_bsum(act ? v : 0.0, red); };
+    // Σ over the block of v at the active entries (a lane gives lo + hi)
+    auto bsum = [&](const double (&v)[E]) -> double {
+        double t = act[0] ? v[0] : 0.0;
+#pragma unroll
+        for (int h = 1; h < E; ++h) t += act[h] ? v[h] : 0.0;
+        return onewg_bsum(t, red);
+    };
     double* __restrict__ usave = reinterpret_cast<double*>(a.u_save);
-    auto put = [&](int64_t si, double v) {
-        if (!act) return;
-        if (!sens) {
-            if (usave) usave[si * n + l] = v;
-        } else if (s_save) {
-            s_save[(si * P + kq) * n + l] = v;
+    auto put = [&](int64_t si, const double (&v)[E]) {
+#pragma unroll
+        for (int h = 0; h < E; ++h) {
+            if (!act[h]) continue;
+            if (!sens) {
+                if (usave) usave[si * n + e[h]] = v[h];
+            } else if (s_save) {
+                s_save[(si * P + kq) * n + e[h]] = v[h];
+            }
         }
     };
-    // this wave's entry of the Dual state (the value, or partial kq) and its seven stage values
-    double z = sens ? 0.0 : (act ? u0[l] : 0.0);
-    double k[7];
-    k[0] = F(z, 0);
+    // this wave's entries of the Dual state (the value, or partial kq) and their seven stage values.  E = 2: the
+    // upper entry's stage values (rows 0-6), and inside the step loop both entries' state and norm (rows 7-10), are
+    // parked in LDS ([waves][11][64], this lane's own column: no other thread reads it), so that what is carried
+    // across an evaluation fits the 168 registers of G + 2 = 12 waves
+    double z[E], kr[7], sq[E], fr[E];
+    double* kl = shv + 2 * 3 * W + w * 11 * kWave + l;
+    auto k = [&](int q, int h) -> double {
+        if constexpr (E == 1) return kr[q];
+        else return h == 0 ? kr[q] : kl[q * kWave];
+    };
+    auto kset = [&](int q, const double (&r)[E]) {
+        kr[q] = r[0];
+        if constexpr (E > 1) kl[q * kWave] = r[1];
+    };
+#pragma unroll
+    for (int h = 0; h < E; ++h) z[h] = sens ? 0.0 : (act[h] ? u0[e[h]] : 0.0);
+    // (slot 1: stage 0 of the first step follows on slot 0; when the step is fixed no barrier lies in between)
+    F(z, 1, fr);
+    kset(0, fr);
     const double t0 = a.t0, tf = a.tf;
     const double ntot = (double)n * (double)(P + 1);
     int64_t si = 0;
@@ -272,47 +350,101 @@ fk_small_fsens_kernel(const LayerConst* __restrict__ lcp, const double* __restri
         put(si, z);
         ++si;
     }
-    double nrm = 0.0;   // ‖u_i‖ of this lane's entry (the Dual norm over value and partials)
-    if (a.adaptive) nrm = ::sqrt(pt_sum(act ? z * z : 0.0));
+    double nrm[E];   // ‖u_i‖ of each of this lane's entries (the Dual norm over value and partials)
+#pragma unroll
+    for (int h = 0; h < E; ++h) nrm[h] = 0.0;
+    if (a.adaptive) {
+#pragma unroll
+        for (int h = 0; h < E; ++h) sq[h] = z[h] * z[h];
+        pt_sum(sq, nrm);
+#pragma unroll
+        for (int h = 0; h < E; ++h) nrm[h] = ::sqrt(nrm[h]);
+    }
     double dt = a.dt;
     if (a.adaptive && !(a.dt > 0)) {   // Hairer & Wanner over the Dual state
-        const double sk = ::fma(a.reltol, nrm, a.abstol);
-        const double e0 = z / sk, e1 = k[0] / sk;
-        const double d0 = ::sqrt(bsum(e0 * e0) / ntot);
-        const double d1 = ::sqrt(bsum(e1 * e1) / ntot);
+        double sk[E], y1[E], f1[E];
+#pragma unroll
+        for (int h = 0; h < E; ++h) {
+            sk[h] = ::fma(a.reltol, nrm[h], a.abstol);
+            const double e0 = z[h] / sk[h];
+            sq[h] = e0 * e0;
+        }
+        const double d0 = ::sqrt(bsum(sq) / ntot);
+#pragma unroll
+        for (int h = 0; h < E; ++h) {
+            const double e1 = k(0, h) / sk[h];
+            sq[h] = e1 * e1;
+        }
+        const double d1 = ::sqrt(bsum(sq) / ntot);
         double dt0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
         dt0 = ::fmin(dt0, tf - t0);
-        const double f1 = F(::fma(dt0, k[0], z), 1);
-        const double e = ::fma(-1.0, k[0], f1) / sk;
-        const double d2 = ::sqrt(bsum(e * e) / ntot) / dt0;
+#pragma unroll
+        for (int h = 0; h < E; ++h) y1[h] = ::fma(dt0, k(0, h), z[h]);
+        F(y1, 1, f1);
+#pragma unroll
+        for (int h = 0; h < E; ++h) {
+            const double er = ::fma(-1.0, k(0, h), f1[h]) / sk[h];
+            sq[h] = er * er;
+        }
+        const double d2 = ::sqrt(bsum(sq) / ntot) / dt0;
         const double mx = ::fmax(d1, d2);
         const double dt1 = mx <= 1e-15 ? ::fmax(1e-6, dt0 * 1e-3) : ::pow(0.01 / mx, 1.0 / 5.0);
         dt = ::fmin(::fmin(100 * dt0, dt1), tf - t0);
+    }
+    auto zv = [&](int h) -> double {   // (the step loop's reads of the state and its norm)
+        if constexpr (E == 1) return z[0];
+        else return kl[(h == 0 ? 9 : 7) * kWave];
+    };
+    auto nv = [&](int h) -> double {
+        if constexpr (E == 1) return nrm[0];
+        else return kl[(h == 0 ? 10 : 8) * kWave];
+    };
+    if constexpr (E > 1) {
+        kl[7 * kWave] = z[1];
+        kl[8 * kWave] = nrm[1];
+        kl[9 * kWave] = z[0];
+        kl[10 * kWave] = nrm[0];
     }
     double qold = a.qoldinit, t = t0;
     int64_t naccept = 0, nreject = 0, nf = 0, it = 0, status = 0;
     for (; it < a.maxiters; ++it) {
         if (t >= tf - 1e-14 * ::fmax(1.0, ::fabs(tf))) break;
         dt = ::fmin(dt, tf - t);
-        double y = z;
+        double y[E];
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
-            y = z;
 #pragma unroll
-            for (int q = 0; q <= i; ++q) y = ::fma(dt * K::TA[i][q], k[q], y);
-            k[i + 1] = F(y, i & 1);
+            for (int h = 0; h < E; ++h) {
+                y[h] = zv(h);
+#pragma unroll
+                for (int q = 0; q <= i; ++q) y[h] = ::fma(dt * K::TA[i][q], k(q, h), y[h]);
+            }
+            F(y, i & 1, fr);
+            kset(i + 1, fr);
         }
         nf += 6;
-        double dtnew = dt, nn = nrm;
-        if (a.adaptive) {
-            double ev = 0.0;
+        double dtnew = dt, nn[E];
 #pragma unroll
-            for (int q = 0; q < 6; ++q) ev = ::fma(dt * K::BT[q], k[q], ev);
-            const double e = ::fma(dt * K::BT[6], k[6], ev);
-            nn = ::sqrt(pt_sum(act ? y * y : 0.0));
-            const double sk = ::fma(a.reltol, ::fmax(nrm, nn), a.abstol);
-            const double r = e / sk;
-            const double eest = ::sqrt(bsum(r * r) / ntot);
+        for (int h = 0; h < E; ++h) nn[h] = nv(h);
+        if (a.adaptive) {
+            double er[E];
+#pragma unroll
+            for (int h = 0; h < E; ++h) {
+                double ev = 0.0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) ev = ::fma(dt * K::BT[q], k(q, h), ev);
+                er[h] = ::fma(dt * K::BT[6], k(6, h), ev);
+                sq[h] = y[h] * y[h];
+            }
+            pt_sum(sq, nn);
+#pragma unroll
+            for (int h = 0; h < E; ++h) {
+                nn[h] = ::sqrt(nn[h]);
+                const double sk = ::fma(a.reltol, ::fmax(nv(h), nn[h]), a.abstol);
+                const double r = er[h] / sk;
+                sq[h] = r * r;
+            }
+            const double eest = ::sqrt(bsum(sq) / ntot);
             const double q11 = eest > 0 ? ::pow(eest, a.beta1) : 0.0;
             if (eest > 1.0 && dt > a.dtmin) {
                 ++nreject;
@@ -328,13 +460,18 @@ fk_small_fsens_kernel(const LayerConst* __restrict__ lcp, const double* __restri
         const double tn = t + dt;
         while (si < a.n_save && a.saveat[si] <= tn + 1e-12 * ::fmax(1.0, ::fabs(tn))) {
             const double tsv = a.saveat[si];
-            double v = y;
+            double v[E];
+#pragma unroll
+            for (int h = 0; h < E; ++h) v[h] = y[h];
             if (!(::fabs(tsv - tn) <= 1e-12 * ::fmax(1.0, ::fabs(tn)))) {
                 double wt[7];
                 tsit5_interp_weights((tsv - t) / dt, wt);
-                v = z;
 #pragma unroll
-                for (int q = 0; q < 7; ++q) v = ::fma(wt[q] * dt, k[q], v);
+                for (int h = 0; h < E; ++h) {
+                    v[h] = zv(h);
+#pragma unroll
+                    for (int q = 0; q < 7; ++q) v[h] = ::fma(wt[q] * dt, k(q, h), v[h]);
+                }
             }
             put(si, v);
             ++si;
@@ -343,9 +480,17 @@ fk_small_fsens_kernel(const LayerConst* __restrict__ lcp, const double* __restri
             a.ts[naccept] = t;
             a.dts[naccept] = dt;
         }
-        z = y;   // commit (value and partials), FSAL
-        k[0] = k[6];
-        nrm = nn;
+        kr[0] = kr[6];   // commit (value and partials), FSAL
+        if constexpr (E == 1) {
+            z[0] = y[0];
+            nrm[0] = nn[0];
+        } else {
+            kl[0] = kl[6 * kWave];
+            kl[7 * kWave] = y[1];
+            kl[8 * kWave] = nn[1];
+            kl[9 * kWave] = y[0];
+            kl[10 * kWave] = nn[0];
+        }
         t = tn;
         ++naccept;
         dt = dtnew;
@@ -436,27 +581,39 @@ hipError_t launch_fk_small_adjoint(const LayerConst& hlc, const PPConst& hpc, co
 }
 #undef KAN_SMALL_GO
 
-bool fk_small_fsens_supported(const LayerConst& hlc, int Nx, int64_t B) {
+// wide (KANODE_OPT_FSENS_WIDE): 0 = the one-entry kernel alone (Nx·B <= 64); 1 = the two-entry kernel above 64
+// entries, up to 128; 2 = the two-entry kernel for every Nx·B <= 128 (tests)
+bool fk_small_fsens_supported(const LayerConst& hlc, int Nx, int64_t B, int wide) {
     const int P = hlc.G + 1;
-    return Nx >= 3 && B >= 1 && (int64_t)Nx * B <= kWave && P + 1 <= kFsensMaxWaves && hlc.basis == BASIS_RBF &&
-           hlc.use_base && (hlc.G == 10 || hlc.G == 5) && (hlc.norm == NORM_SOFTSIGN || hlc.norm == NORM_TANH_FAST);
+    return Nx >= 3 && B >= 1 && (int64_t)Nx * B <= (wide ? 2 : 1) * kWave && P + 1 <= kFsensMaxWaves &&
+           hlc.basis == BASIS_RBF && hlc.use_base && (hlc.G == 10 || hlc.G == 5) &&
+           (hlc.norm == NORM_SOFTSIGN || hlc.norm == NORM_TANH_FAST);
 }
 
 hipError_t launch_fk_small_fsens(const LayerConst& hlc, const PPConst& hpc, bool tab, const LayerConst* lc,
                                  const double* p, const double* tables, const FkSmallArgs& s, const double* u0,
-                                 int64_t B, const ChainSolveArgs& a, double* s_save, hipStream_t st) {
-    if (!fk_small_fsens_supported(hlc, s.Nx, B) || (tab && (!hpc.enabled || s.ni != hpc.ni || !tables)))
+                                 int64_t B, const ChainSolveArgs& a, double* s_save, int wide, hipStream_t st) {
+    if (!fk_small_fsens_supported(hlc, s.Nx, B, wide) || (tab && (!hpc.enabled || s.ni != hpc.ni || !tables)))
         return hipErrorNotSupported;
     const int threads = (hlc.G + 2) * kWave;
+    const bool two = wide == 2 || (int64_t)s.Nx * B > kWave;   // entries per lane
     const size_t lds = (tab ? 3 * sizeof(double2) * (kPPCoef / 2) * (size_t)hpc.ni : 0) +
-                       sizeof(double) * (size_t)(kFsensMaxWaves + 6) * kWave;   // exchange + the two slots
-#define KAN_FSENS1(NORM, GT, TAB)                                                                                  \
+                       (two ? sizeof(double) * ((size_t)(hlc.G + 2 + 6) * 2 * kWave +   // exchange + the two slots
+                                                11 * (size_t)threads)                  // + the parked state
+                            : sizeof(double) * (size_t)(kFsensMaxWaves + 6) * kWave);
+    if (lds > 150 * 1024) return hipErrorNotSupported;
+#define KAN_FSENS2(NORM, GT, TAB, E)                                                                               \
     do {                                                                                                         \
-        const void* fn = reinterpret_cast<const void*>(&fk_small_fsens_kernel<NORM, GT, TAB>);                   \
+        const void* fn = reinterpret_cast<const void*>(&fk_small_fsens_kernel<NORM, GT, TAB, E>);                \
         hipError_t e_ = ensure_dynamic_lds(fn, lds);                                                             \
         if (e_ != hipSuccess) return e_;                                                                         \
-        hipLaunchKernelGGL((fk_small_fsens_kernel<NORM, GT, TAB>), dim3(1), dim3(threads), lds, st, lc, p,         \
+        hipLaunchKernelGGL((fk_small_fsens_kernel<NORM, GT, TAB, E>), dim3(1), dim3(threads), lds, st, lc, p,      \
                            (const double2*)tables, s, u0, B, a, s_save);                                         \
+    } while (0)
+#define KAN_FSENS1(NORM, GT, TAB)                                                                                  \
+    do {                                                                                                         \
+        if (two) KAN_FSENS2(NORM, GT, TAB, 2);                                                                   \
+        else KAN_FSENS2(NORM, GT, TAB, 1);                                                                       \
     } while (0)
 #define KAN_FSENS(NORM, GT)                                                                                        \
     do {                                                                                                         \
@@ -469,6 +626,7 @@ hipError_t launch_fk_small_fsens(const LayerConst& hlc, const PPConst& hpc, bool
     else KAN_FSENS(NORM_TANH_FAST, 5);
 #undef KAN_FSENS
 #undef KAN_FSENS1
+#undef KAN_FSENS2
     return hipGetLastError();
 }
 

@@ -72,6 +72,7 @@ struct kanode_handle {
     bool chain_wide = true;           // KANODE_OPT_CHAIN_WIDE
     bool record_adj_steps = false;    // KANODE_OPT_RECORD_ADJOINT_STEPS
     bool fk_loop = true;              // KANODE_OPT_FK_DEVICE_LOOP
+    int fsens_wide = 0;               // KANODE_OPT_FSENS_WIDE
     std::vector<double> adj_steps;    // the last kanode_adjoint_tsit5's accepted step sizes (when recorded)
     bool adj_fused_finish = false;    // KANODE_OPT_ADJ_FUSED_FINISH (measured even with the finish launch)
     unsigned* fin_ctr = nullptr;      // its two arrival counters (device, zeroed at allocation)
@@ -1107,6 +1108,7 @@ kanode_status kanode_set_option(kanode_handle* h, int32_t option, int64_t value)
     case KANODE_OPT_CHAIN_WIDE: return flag(h->chain_wide, "CHAIN_WIDE");
     case KANODE_OPT_RECORD_ADJOINT_STEPS: return flag(h->record_adj_steps, "RECORD_ADJOINT_STEPS");
     case KANODE_OPT_FK_DEVICE_LOOP: return flag(h->fk_loop, "FK_DEVICE_LOOP");
+    case KANODE_OPT_FSENS_WIDE: return count(h->fsens_wide, "FSENS_WIDE", 2);
     }
     return fail(h, KANODE_ERR_INVALID_ARG, "unknown option " + std::to_string(option));
 }
@@ -1133,6 +1135,7 @@ int64_t kanode_get_option(const kanode_handle* h, int32_t option) {
     case KANODE_OPT_CHAIN_WIDE: return h->chain_wide ? 1 : 0;
     case KANODE_OPT_RECORD_ADJOINT_STEPS: return h->record_adj_steps ? 1 : 0;
     case KANODE_OPT_FK_DEVICE_LOOP: return h->fk_loop ? 1 : 0;
+    case KANODE_OPT_FSENS_WIDE: return h->fsens_wide;
     }
     return -1;
 }
@@ -1813,7 +1816,7 @@ int kanode_internal_pair_adjoint_workgroups(const kanode_handle* h, int64_t batc
 // forward sensitivities of a small Fisher-KPP field (kan_small.hip fk_small_fsens_kernel)
 bool kanode_internal_fsens_ok(const kanode_handle* h, int64_t batch) {
     return h->spec.rhs_kind == KANODE_RHS_POINTWISE_PERIODIC_LAPLACIAN && h->spec.dtype == KANODE_F64 &&
-           kan::fk_small_fsens_supported(h->hlc[0], (int)h->spec.nx, batch);
+           kan::fk_small_fsens_supported(h->hlc[0], (int)h->spec.nx, batch, h->fsens_wide);
 }
 kanode_status kanode_internal_fk_fsens(kanode_handle* h, const void* p, const void* u0, int64_t batch,
                                        const kan::ChainSolveArgs* a, void* s_save, void* stream) {
@@ -1825,7 +1828,7 @@ kanode_status kanode_internal_fk_fsens(kanode_handle* h, const void* p, const vo
     }
     const hipError_t e = kan::launch_fk_small_fsens(h->hlc[0], h->hpc, tab, h->dlc, (const double*)p,
                                                     tab ? h->dtable : nullptr, fk_small_args(h), (const double*)u0,
-                                                    batch, *a, (double*)s_save, st);
+                                                    batch, *a, (double*)s_save, h->fsens_wide, st);
     if (e == hipErrorNotSupported)
         return fail(h, KANODE_ERR_UNSUPPORTED, "forward sensitivities: shape not covered by the one-workgroup kernel");
     if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_fk_small_fsens: ") + hipGetErrorString(e));

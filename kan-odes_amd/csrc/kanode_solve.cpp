@@ -2173,7 +2173,7 @@ extern "C" kanode_status kanode_forward_sensitivity_tsit5(kanode_handle* h, cons
     if (!kanode_internal_fsens_ok(h, batch))
         return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
                                     "forward sensitivities: a Fisher-KPP (pointwise + periodic Laplacian) fp64 RHS with "
-                                    "nx * batch <= 64, rbf basis, G = 5 or 10, base activation, softsign / tanh_fast");
+                                    "nx * batch <= 64 (128 with KANODE_OPT_FSENS_WIDE), rbf basis, G = 5 or 10, base activation, softsign / tanh_fast");
     hipStream_t st = (hipStream_t)stream;
     if (capturing(st)) return kanode_internal_fail(h, KANODE_ERR_CAPTURE, "forward sensitivities read their counters");
     const int64_t n = kanode_internal_state_length(h) * batch;

@@ -99,6 +99,7 @@ OPT_LAST_ADJOINT = 16      # read-only: a kanode_adjoint_path value
 OPT_CHAIN_WIDE = 17
 OPT_RECORD_ADJOINT_STEPS = 18
 OPT_FK_DEVICE_LOOP = 19
+OPT_FSENS_WIDE = 20        # 0 / 1 / 2 (include/kanode.h)
 ADJ_NONE, ADJ_HOST_LOOP, ADJ_CHAIN_WG, ADJ_PAIR_PERSIST, ADJ_PAIR_FALLBACK = 0, 1, 2, 3, 4   # kanode_adjoint_path
 TRAIN_STOP = {0: "ok", 1: "forward_maxiters", 2: "dense_capacity", 3: "adjoint_maxiters", 4: "loss_not_finite",
               5: "test_maxiters"}   # kanode_train_stop
@@ -109,7 +110,7 @@ OPTIONS = {"pointwise_table": OPT_POINTWISE_TABLE, "fused_step": OPT_FUSED_STEP,
            "adj_fused_finish": OPT_ADJ_FUSED_FINISH, "pair_persist_max_wg": OPT_PAIR_PERSIST_MAX_WG,
            "pair_persist_abort": OPT_PAIR_PERSIST_ABORT, "last_adjoint": OPT_LAST_ADJOINT,
            "chain_wide": OPT_CHAIN_WIDE, "record_adjoint_steps": OPT_RECORD_ADJOINT_STEPS,
-           "fk_device_loop": OPT_FK_DEVICE_LOOP}
+           "fk_device_loop": OPT_FK_DEVICE_LOOP, "fsens_wide": OPT_FSENS_WIDE}
 
 SIGNATURES = [
     ("kanode_create", C.c_int, [C.POINTER(SpecC), C.POINTER(C.c_void_p)]),

@@ -285,14 +285,23 @@ def forward_ok(f, u0: torch.Tensor, p) -> bool:
     """The sensealg SciMLSensitivity 7.69 picks automatically for a hand-written ODEProblem (Fisher-KPP_Source.jl:198,
     the Allen-Cahn source driver: no sensealg given) is ForwardDiffSensitivity when length(u0) + length(p) <= 100
     (third-party rule, restated).  True when that applies and the native forward-sensitivity solve
-    covers the shape."""
+    covers the shape.  Once the rule has passed, the handle's `fsens_wide` option is turned on (where it is off), so
+    that fields of 65 to 128 entries are served by the two-entries-per-lane kernel and the choice is the
+    reference's over the whole rule; setting it again is idempotent, and a value the caller chose (2) is kept."""
     hd = getattr(f, "hd", None)
     if hd is None or not getattr(f, "auto_sensealg", False) or not isinstance(p, torch.Tensor) or not u0.is_cuda:
         return False
     if u0.numel() + p.numel() > 100:
         return False
+    enable_wide_forward(hd)
     B = u0.shape[0] if u0.dim() == 2 else 1
     return hd.forward_sensitivity_supported(B)
+
+
+def enable_wide_forward(hd) -> None:
+    """Turn the handle's `fsens_wide` option on where it is off (idempotent)."""
+    if hd.get_option("fsens_wide") == 0:
+        hd.set_option("fsens_wide", 1)
 
 
 def _contract(S: torch.Tensor, dl: torch.Tensor) -> torch.Tensor:

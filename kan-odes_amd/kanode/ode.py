@@ -216,10 +216,11 @@ def solve(f, u0: torch.Tensor, tspan, p: torch.Tensor, saveat=None, opt: Tsit5Op
       sensealg="interpolating_adjoint" SciMLSensitivity's InterpolatingAdjoint, the reference's
                                        default (kanode.adjoint; f needs `vjp_stage`);
       sensealg="forward"               ForwardDiffSensitivity (gradient w.r.t. p; the native one-workgroup
-                                       forward-sensitivity solve of a small Fisher-KPP field);
+                                       forward-sensitivity solve of a small Fisher-KPP field, up to 128
+                                       entries: the handle's fsens_wide option is turned on);
       sensealg="auto"                  SciMLSensitivity's automatic choice for a hand-written ODEProblem:
-                                       "forward" where length(u0) + length(p) <= 100 and covered, else
-                                       "interpolating_adjoint".
+                                       "forward" where length(u0) + length(p) <= 100 and covered (and u0
+                                       needs no gradient), else "interpolating_adjoint".
     dense_record: an adjoint.DenseRecord that receives every accepted step."""
     opt = opt or Tsit5Options()
     t0, tf = float(tspan[0]), float(tspan[1])
@@ -233,10 +234,13 @@ def solve(f, u0: torch.Tensor, tspan, p: torch.Tensor, saveat=None, opt: Tsit5Op
         saveat = [s for s in saveat if s <= tf + tol]
     if sensealg == "auto":   # SciMLSensitivity's automatic choice for a hand-written ODEProblem (adjoint.forward_ok)
         from .adjoint import forward_ok
-        sensealg = "forward" if native and forward_ok(f, u0, p) else "interpolating_adjoint"
+        # (forward mode differentiates with respect to p alone: a gradient for u0 takes the adjoint)
+        sensealg = "forward" if native and not u0.requires_grad and forward_ok(f, u0, p) else "interpolating_adjoint"
     if sensealg == "forward" and grad:
-        from .adjoint import forward_ok, solve_forward_sensitivity
+        from .adjoint import enable_wide_forward, solve_forward_sensitivity
         hd = getattr(f, "hd", None)
+        if native and hd is not None:
+            enable_wide_forward(hd)
         if not native or hd is None or not hd.forward_sensitivity_supported(u0.shape[0] if u0.dim() == 2 else 1):
             raise ValueError("sensealg='forward' needs the native forward-sensitivity solve (a small Fisher-KPP field, "
                              "kanode_forward_sensitivity_supported)")
