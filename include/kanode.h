@@ -460,6 +460,40 @@ kanode_status kanode_train_tsit5(kanode_handle* h, void* p, void* m, void* v, co
                                  int64_t n_iters, double* loss, double* loss_test, void* grad, void* p_before,
                                  int64_t* counts, int64_t* iters_done, int32_t* stop_reason, void* stream);
 
+/* --- the device-resident training loop of a small Fisher-KPP field on the forward-mode gradient -----
+ * n_iters whole iterations of the reference's Fisher-KPP / Allen-Cahn source drivers (PDE examples/
+ * Fisher-KPP_Source.jl:194-213) in ONE kernel launch.  Iteration it = 0 .. n_iters-1, in order:
+ *     the pointwise tables at p_it (where the handle uses them)            (the table build's arithmetic)
+ *     ForwardDiffSensitivity solve at p_it over (t0, tf)                   (kanode_forward_sensitivity_tsit5's)
+ *     loss[it] = mean((u_save - target)²)                                  -- the loss AT p_it, before the update
+ *     dp_k = Σ_j Σ_i (u_save - target)_ji·2/numel · ∂u_ji/∂p_k, summed per lane in saveat order, then over the wave
+ *     p, m, v <- Adam(p_it, m, v, dp) with the running powers βp           (kanode_adam_step's, scale = 1)
+ *     loss_test[it] = mean((u(saveat_test) - target_test)²) of the plain solve over (t0, tf_test) at p_{it+1},
+ *                     the parameters AFTER the update (kanode_solve_tsit5's one-workgroup arithmetic; the drivers'
+ *                     logged loss(p)), when a test problem is given
+ * The arguments, their ownership, beta1_t / beta2_t, the stop rule, the synchronising return, *iters_done,
+ * *stop_reason and the kanode_last_error text are those of kanode_train_tsit5, with u0 [batch][nx], target
+ * [n_save][batch][nx], target_test [n_save_test][batch][nx] and counts [n_iters][4] (int64: the sensitivity solve's
+ * naccept, nreject, then those of the iteration's logged-loss solve; the call writes the second pair only when a
+ * test problem is given -- there is no adjoint -- so zero the array to read zeros there).  The stops are
+ * KANODE_TRAIN_FORWARD_MAXITERS, KANODE_TRAIN_LOSS_NOT_FINITE
+ * and KANODE_TRAIN_TEST_MAXITERS.  The saveat copies live on the handle and are reused by later calls.
+ *
+ * Covered: kanode_train_forward_supported(h, batch, 0) is kanode_forward_sensitivity_supported(h, batch) and
+ * follows KANODE_OPT_FSENS_WIDE; with_test = 1 additionally needs the one-workgroup plain solve (even nx <= 64, the
+ * pointwise table and KANODE_OPT_FUSED_SOLVE on) and batch <= G + 2.  Anything else, and n_save_test > 0 on a shape
+ * without that solve: KANODE_ERR_UNSUPPORTED, nothing launched.  kanode_train_tsit5 / kanode_train_supported keep
+ * their meaning: a Fisher-KPP handle is not theirs. */
+int32_t kanode_train_forward_supported(const kanode_handle* h, int64_t batch, int32_t with_test);
+kanode_status kanode_train_forward_tsit5(kanode_handle* h, void* p, void* m, void* v, const void* u0, int64_t batch,
+                                         double t0, double tf, const double* saveat, int64_t n_save,
+                                         const void* target, double tf_test, const double* saveat_test,
+                                         int64_t n_save_test, const void* target_test,
+                                         const kanode_solver_options* opt, double eta, double beta1, double beta2,
+                                         double eps, double beta1_t, double beta2_t, int64_t n_iters, double* loss,
+                                         double* loss_test, void* grad, void* p_before, int64_t* counts,
+                                         int64_t* iters_done, int32_t* stop_reason, void* stream);
+
 /* --- the data-parallel gradient all-reduce (one process per GPU) -----------------
  * For hosts without a collective of their own (Julia, C): after kanode_adjoint_tsit5 on each rank's
  * trajectory shard, the flat [dp; L] is SUM all-reduced in place over RCCL (xGMI inside a node), then

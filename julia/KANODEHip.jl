@@ -467,6 +467,41 @@ function train_tsit5!(h::Handle, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cvoid}, u0
     return done[], stop[]
 end
 
+# --- the device-resident Fisher-KPP loop on the forward-mode gradient (kanode_train_forward_tsit5): n_iters
+# iterations of Fisher-KPP_Source.jl:194-213 (tables, ForwardDiffSensitivity solve, loss, gradient, Flux Adam, the
+# logged loss(p) solve) in one kernel launch, for the shapes of fsens_supported.  u0 is B x nx, target
+# n_save x B x nx (device pointers); counts is n_iters x 4 (Int64: the sensitivity solve's naccept, nreject, then the
+# logged-loss solve's, written only with a test problem: zero the buffer first).
+train_forward_supported(h::Handle, B::Integer, with_test::Bool = false) =
+    ccall(sym(:kanode_train_forward_supported), Int32, (Ptr{Cvoid}, Int64, Int32), h.ptr, B, with_test ? 1 : 0) == 1
+
+"""train_forward_tsit5!(h, p, m, v, u0, B, tspan, saveat, target, n_iters, loss; η, β, ϵ, βp, test, loss_test, grad,
+p_before, counts, opt) -> (iters_done, stop_reason): train_tsit5! for a small Fisher-KPP field of B trajectories.
+loss[it] is the loss at p_it (before the update), loss_test[it] the logged loss at p_{it+1}; test = (tf_test,
+saveat_test, target_test) needs train_forward_supported(h, B, true)."""
+function train_forward_tsit5!(h::Handle, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cvoid}, u0::Ptr{Cvoid}, B::Integer,
+                              tspan, saveat::Vector{Float64}, target::Ptr{Cvoid}, n_iters::Integer,
+                              loss::Ptr{Cvoid}; η::Real = 1e-2, β = (0.9, 0.999), ϵ::Real = 1e-8, βp = β,
+                              test = nothing, loss_test::Ptr{Cvoid} = C_NULL, grad::Ptr{Cvoid} = C_NULL,
+                              p_before::Ptr{Cvoid} = C_NULL, counts::Ptr{Cvoid} = C_NULL,
+                              opt::SolverOptions = default_options(), stream::Ptr{Cvoid} = C_NULL)
+    train_forward_supported(h, B, test !== nothing) ||
+        throw(ArgumentError("train_forward_tsit5!: not covered for this handle"))
+    issorted(saveat) || throw(ArgumentError("saveat must be ascending"))
+    tf_t, sv_t, tg_t = test === nothing ? (0.0, Float64[], Ptr{Cvoid}(C_NULL)) : (Float64(test[1]), Vector{Float64}(test[2]), test[3])
+    done = Ref{Int64}(0)
+    stop = Ref{Int32}(0)
+    st = GC.@preserve saveat sv_t ccall(sym(:kanode_train_forward_tsit5), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float64}, Int64,
+         Ptr{Cvoid}, Float64, Ptr{Float64}, Int64, Ptr{Cvoid}, Ref{SolverOptions}, Float64, Float64, Float64, Float64,
+         Float64, Float64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}, Ref{Int32},
+         Ptr{Cvoid}),
+        h.ptr, p, m, v, u0, B, tspan[1], tspan[2], saveat, length(saveat), target, tf_t, sv_t, length(sv_t), tg_t,
+        opt, η, β[1], β[2], ϵ, βp[1], βp[2], n_iters, loss, loss_test, grad, p_before, counts, done, stop, stream)
+    stop[] == 0 && check(h, st)
+    return done[], stop[]
+end
+
 # --- data-parallel training across GPUs (kanode_comm_*): one process per GPU, each with its trajectory
 # shard; after the adjoint, the flat [dp; L] (device) is SUM all-reduced over RCCL and the mean applied by
 # kanode_adam_step(scale = 1/nranks).  Rank 0 calls comm_unique_id() and the host distributes the bytes

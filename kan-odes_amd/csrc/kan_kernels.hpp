@@ -474,7 +474,7 @@ struct ChainTrainArgs {
     const double* saveat;          // [n_save] (device)
     const double* target;          // [n_save][2]
     int64_t n_save;
-    double dl_scale;               // 2 / (n_save·2)
+    double dl_scale;               // 2 / numel(target): 2 / (n_save·2), the Fisher-KPP loop 2 / (n_save·nx·batch)
     const double* stops;           // the adjoint's jump groups (one_launch_adj_args' layout)
     const int32_t* jrows;
     const int32_t* joff;
@@ -489,12 +489,14 @@ struct ChainTrainArgs {
     double* p;                     // [P] in/out
     double* m;                     // [P] in/out
     double* v;                     // [P] in/out
-    double* rec;                   // [cap·7·2 + 2] dense output and k1_0 when !stage_rec (else unused)
+    double* rec;                   // [cap·7·2 + 2] dense output and k1_0 when !stage_rec (else unused); the
+                                   // Fisher-KPP loop: [kFsensMaxWaves][128] accumulators at two entries per lane
     double* loss;                  // [n_iters]
     double* loss_test;             // [n_iters] or null
     double* grad;                  // [n_iters][P] or null
     double* p_before;              // [n_iters][P] or null
-    int64_t* counts;               // [n_iters][4] or null: forward naccept/nreject, adjoint naccept/nreject
+    int64_t* counts;               // [n_iters][4] or null: forward naccept/nreject, adjoint naccept/nreject (the
+                                   // Fisher-KPP loop: the logged-loss solve's in place of the adjoint's)
     int64_t* out;                  // iters_done, ChainTrainStop
 };
 bool chain_train_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B, size_t esize, bool wide);
@@ -503,6 +505,21 @@ bool chain_train_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B,
 size_t chain_train_lds(int64_t cap, int64_t n_save, int64_t n_save_test, int* stage_rec);
 hipError_t launch_kd_chain_train(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P,
                                  const ChainTrainArgs& a, hipStream_t st);
+// K whole training iterations of a small Fisher-KPP field on the forward-mode gradient in ONE launch
+// (fk_small_train_kernel, kan_small_train.hip; Fisher-KPP_Source.jl:194-213): per iteration the tables at p_it
+// (pp_build_block, with tab), the Dual solve of fk_small_fsens_kernel with loss[it] and the gradient accumulated at
+// its saveat stops, the Adam step (adam_entry) and, with a test problem, the plain solve over (t0, tf_test) at
+// p_{it+1} for loss_test[it] (fk_small_tsit5_kernel's arithmetic).  The arguments are ChainTrainArgs' (u0 [Nx·B],
+// target [n_save][Nx·B]; counts is [n_iters][4]: the Dual solve's naccept, nreject, then the logged-loss solve's,
+// which the kernel writes only with a test problem); rec is the accumulators' column block at two entries per lane; cap, stage_rec, rec and the
+// adjoint's jump groups are not used, and the stops are kTrainForwardMaxiters, kTrainLossNotFinite and
+// kTrainTestMaxiters.  Covers the shapes of launch_fk_small_fsens; with a test problem also those of
+// launch_fk_small_tsit5 at B <= G + 2.
+bool fk_small_train_supported(const LayerConst& hlc, const PPConst& hpc, bool tab, int Nx, int64_t B, int wide,
+                              bool with_test);
+hipError_t launch_fk_small_train(const LayerConst& hlc, const PPConst& hpc, bool tab, const LayerConst* lc,
+                                 const PPConst* pc, const FkSmallArgs& s, int64_t B, const ChainTrainArgs& a, int wide,
+                                 hipStream_t st);
 // A whole InterpolatingAdjoint step of a small chain per trajectory column (kd_chain_vjp_step_kernel, kan_col.hip):
 // the six adjoint stages of kanode_solve.cpp adjoint_t in one launch, λ and kλ_1..kλ_7 of a column in registers.
 // Stage s reads the forward dense output u_i + Σ_q su_c[s][q] k_{i,q} (K form, the forward step holding stage s)

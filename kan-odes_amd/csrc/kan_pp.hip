@@ -22,6 +22,7 @@
 #include "kan_kernels.hpp"
 #include "kan_lap.hpp"
 #include "kan_pp_point.hpp"
+#include "kan_pp_build.hpp"
 #include "kan_adjloop.hpp"
 #include "kan_tsit5.hpp"
 
@@ -56,11 +57,10 @@ __device__ unsigned long long kan_clock_probe[32];
 #define KAN_PROBE_ADD(slot, val)
 #endif
 
-constexpr int kPPEvals = kPPCoef + kPPChecks;        // direct evaluations per interval
-
 // One block builds kPPPerBlock intervals of one tabulated function (blockIdx.y
 // picks it from `fns`): 13 direct evaluations per interval (10 nodes + 3 checks),
-// node values -> monomial coefficients (Q, host-built), acceptance.
+// node values -> monomial coefficients (Q, host-built), acceptance (pp_build_block, kan_pp_build.hpp;
+// the stamp logic is this kernel's).
 //   PP_PHI    φ(u)  = Σ_j C_j B_j(N(u)) + W swish(u)                 (kdense.jl:116-124)
 //   PP_DPHI   φ'(u) = N'(u) Σ_j ∂B_j C_j / h + W swish'(u)  — the rrule chain of
 //             utils.jl:15-21 and NNlib's Ω-form derivatives, i.e. x̄/λ of the pullback
@@ -87,11 +87,9 @@ fk_pp_build_kernel(const LayerConst* __restrict__ lcp, const PPConst* __restrict
     __shared__ double sT[kPPEvals];              // nodes, then check points
     __shared__ double sC[kMaxGrid + 1];          // C_0..C_{G-1}, W
     __shared__ double sG[kMaxGrid];              // knots
-    __shared__ double fv[kPPPerBlock][kPPEvals];
-    __shared__ double sv[kPPPerBlock][kPPChecks];
-    __shared__ double cf[kPPPerBlock][kPPCoef];
-    __shared__ int bad[kPPPerBlock];
+    __shared__ double scr[kPPBuildScratch];      // the block's scratch (kan_pp_build.hpp)
     __shared__ int same;
+    int* bad = pp_build_bad(scr);
     const LayerConst& lc = *lcp;
     const PPConst& pc = *pcp;
     const int tid = threadIdx.x;
@@ -117,104 +115,18 @@ fk_pp_build_kernel(const LayerConst* __restrict__ lcp, const PPConst* __restrict
     if (same) return;          // (block-uniform)
     const Math<double> M{tab};
     double* __restrict__ table = tables + (int64_t)fn * kPPCoef * pc.ni;
-    const int k0 = blockIdx.x * kPPPerBlock;
-    {
-        // evaluation e = tid / 4 (all lanes of a quad take part in the shuffles)
-        const int e = tid >> 2, sub = tid & 3;
-        const bool live = e < kPPPerBlock * kPPEvals;
-        const int kl = live ? e / kPPEvals : 0, m = live ? e - kl * kPPEvals : 0;
-        const double c = pc.lo + ((double)(k0 + kl) + 0.5) * pc.w;   // exact: w is a power of two
-        const double u = ::fma(sT[m], 0.5 * pc.w, c);
-        const double n = normalize<NORM_RUNTIME, double>(M, lc.norm, u);
-        const double invh = (double)lc.invh;
-        double s = 0.0, a = 0.0, base = 0.0;    // spline-part sum, Σ|spline terms|, base term
-        if (fn != PP_SWISH) {
-            for (int j = sub; j < G; j += 4) {
-                double aux = 0.0;
-                const double y = (n - sG[j]) * invh;
-                const double phi = basis_direct<double>(M, lc.basis, y, aux);
-                const double t = fn == PP_PHI ? sC[j] * phi
-                                              : basis_pull<double>(lc.basis, lc.iqf_quirk, y, phi, aux, sC[j]) * invh;
-                s = s + t;
-                a = a + kabs(t);
-            }
-        }
-        if (sub == 3) {
-            double sw, dsw;
-            swish_and_grad<double>(M, u, sw, dsw);
-            base = fn == PP_SWISH ? sw : (lc.use_base ? sC[G] * (fn == PP_PHI ? sw : dsw) : 0.0);
-        }
-        s = s + __shfl_xor(s, 1, 4);
-        a = a + __shfl_xor(a, 1, 4);
-        s = s + __shfl_xor(s, 2, 4);
-        a = a + __shfl_xor(a, 2, 4);
-        base = __shfl(base, 3, 4);
-        if (live && sub == 0) {
-            // acceptance scale: Σ|terms| at the point, floored at 4·w·(the function's natural
-            // magnitude: Σ|C| (/h) + |W|, or 1 + |u| for swish).  The node -> monomial
-            // conversion rounds at ~|Q|·eps·(variation over the interval, ~w·|f'|), so
-            // where every term vanishes (swish(0) = 0) the floor keeps a correct fit from
-            // being rejected; it admits absolute errors <= 2.5e-15 of that magnitude.
-            // (magnitudes by compare-and-negate: with the |x| source modifier the swish branch's scale came out
-            // as base + 4w(1 + u), negative below u ≈ -0.2, which rejected every swish interval there and sent
-            // those points of the VJP to the direct formula; tools/pp_direct_scan.py)
-            auto mag = [](double x) { return x < 0.0 ? -x : x; };
-            double csum = 0.0;
-            for (int j = 0; j < G; ++j) csum += mag(sC[j]);
-            const double wabs = lc.use_base ? mag(sC[G]) : 0.0;
-            double v, sc, ref;
-            if (fn == PP_PHI) {
-                v = s + base;
-                sc = a + mag(base);
-                ref = csum + wabs;
-            } else if (fn == PP_DPHI) {
-                const double dn = dnormalize<NORM_RUNTIME, double>(lc.norm, n);
-                v = dn * s + base;
-                sc = dn * a + mag(base);
-                ref = csum * invh + wabs;
-            } else {
-                v = base;
-                sc = mag(base);
-                ref = 1.0 + mag(u);
-            }
-            sc += 4.0 * pc.w * ref;
-            fv[kl][m] = v;
-            if (m >= kPPCoef) sv[kl][m - kPPCoef] = sc;
-        }
-    }
-    __syncthreads();
-    if (tid < kPPPerBlock * kPPCoef) {
-        // a = Q (f - f_0) + f_0 e_0: the constant is carried exactly, Q only sees the variation
-        const int kl = tid / kPPCoef, i = tid - kl * kPPCoef;
-        const double f0 = fv[kl][0];
-        double s = 0.0;
-#pragma unroll
-        for (int m = 0; m < kPPCoef; ++m) s = ::fma(sQ[i * kPPCoef + m], fv[kl][m] - f0, s);
-        cf[kl][i] = i == 0 ? s + f0 : s;
-    }
-    __syncthreads();
-    if (tid < kPPPerBlock * kPPChecks) {
-        const int kl = tid / kPPChecks, c = tid - kl * kPPChecks;
-        const double t = sT[kPPCoef + c];
-        double y = cf[kl][kPPCoef - 1];
-#pragma unroll
-        for (int i = kPPCoef - 2; i >= 0; --i) y = ::fma(y, t, cf[kl][i]);
-        if (!(kabs(y - fv[kl][kPPCoef + c]) <= pc.tol * sv[kl][c])) {
-            bad[kl] = 1;
+    const PPBuildLds L{sQ, sT, sC, sG, scr};
 #ifdef KAN_CLOCK_PROBE   // (diagnostic build: rejected intervals per function and the worst residual / tolerance)
-            atomicAdd(&kan_clock_probe[16 + fn], 1ull);
-            const double r = kabs(y - fv[kl][kPPCoef + c]) / (pc.tol * sv[kl][c]);
-            atomicMax(&kan_clock_probe[19], (unsigned long long)__double_as_longlong(r == r ? r : 1e300));
-            atomicMax(&kan_clock_probe[20 + fn], (unsigned long long)(k0 + kl));
+    auto rejected = [](int f_, double y, double f, double tolsc, int k) {
+        atomicAdd(&kan_clock_probe[16 + f_], 1ull);
+        const double r = kabs(y - f) / tolsc;
+        atomicMax(&kan_clock_probe[19], (unsigned long long)__double_as_longlong(r == r ? r : 1e300));
+        atomicMax(&kan_clock_probe[20 + f_], (unsigned long long)k);
+    };
+    pp_build_block(M, lc, pc, L, blockIdx.x, fn, tid, true, table, rejected);
+#else
+    pp_build_block(M, lc, pc, L, blockIdx.x, fn, tid, true, table);
 #endif
-        }
-    }
-    __syncthreads();
-    if (tid < kPPPerBlock * kPPCoef) {
-        const int kl = tid / kPPCoef, i = tid - kl * kPPCoef;
-        const int64_t k = k0 + kl;
-        table[((int64_t)(i >> 1) * pc.ni + k) * 2 + (i & 1)] = bad[kl] ? __builtin_nan("") : cf[kl][i];
-    }
     // this block's stamp (read only by this block of later launches; published to them by the kernel boundary)
     if (tid <= G) stamp[tid] = sC[tid];
     if (tid == 0) {

@@ -96,6 +96,7 @@ struct kanode_handle {
     void* train_buf = nullptr;
     size_t train_bytes = 0;
     std::vector<char> train_meta;
+    size_t train_meta_off = 0;        // where in train_buf those bytes lie
     // table reuse inside one integrator solve (p constant): build each table set once
     bool hold_tables = false;
     bool built_phi = false, built_vjp = false;
@@ -1695,6 +1696,30 @@ bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch) {
     return h->spec.rhs_kind == KANODE_RHS_CHAIN && kanode_internal_chain_tsit5_ok(h, batch) &&
            kan::chain_train_supported(h->hlc, h->n_layers, h->P, batch, h->esize, h->chain_wide);
 }
+// The handle's training-loop buffer: result words | (the LV loop's dense-output block) | meta at off_meta, grown on
+// demand; meta is uploaded only when it differs from the last call's bytes.
+static kanode_status train_buf_stage(kanode_handle* h, size_t off_meta, const std::vector<char>& meta, hipStream_t st,
+                                     char*& base) {
+    const size_t need = off_meta + meta.size() + 64;
+    if (h->train_bytes < need) {
+        HIP_TRY(h, hipStreamSynchronize(st));
+        if (h->train_buf) HIP_TRY(h, hipFree(h->train_buf));
+        h->train_buf = nullptr;
+        h->train_bytes = 0;
+        h->train_meta.clear();
+        h->train_meta_off = 0;
+        HIP_TRY(h, hipMalloc(&h->train_buf, need));
+        h->train_bytes = need;
+    }
+    base = (char*)h->train_buf;
+    if (h->train_meta != meta || h->train_meta_off != off_meta) {
+        // (the earlier calls synchronised, so nothing on the device still reads the old bytes)
+        HIP_TRY(h, hipMemcpy(base + off_meta, meta.data(), meta.size(), hipMemcpyHostToDevice));
+        h->train_meta = meta;
+        h->train_meta_off = off_meta;
+    }
+    return KANODE_OK;
+}
 kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs* a, const std::vector<char>& meta,
                                           int64_t res[2], void* stream) {
     const hipStream_t st = (hipStream_t)stream;
@@ -1725,21 +1750,10 @@ kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs*
         return fail(h, KANODE_ERR_UNSUPPORTED, "kanode_train_tsit5: not supported (saveat lists too long for one workgroup's LDS)");
     const size_t off_rec = 64;
     const size_t off_meta = off_rec + sizeof(double) * ((size_t)kan::kChainAdjointMaxSteps * 7 * 2 + 2);
-    const size_t need = off_meta + meta.size() + 64;
-    if (h->train_bytes < need) {
-        HIP_TRY(h, hipStreamSynchronize(st));
-        if (h->train_buf) HIP_TRY(h, hipFree(h->train_buf));
-        h->train_buf = nullptr;
-        h->train_bytes = 0;
-        h->train_meta.clear();
-        HIP_TRY(h, hipMalloc(&h->train_buf, need));
-        h->train_bytes = need;
-    }
-    char* base = (char*)h->train_buf;
-    if (h->train_meta != meta) {
-        // (the earlier calls synchronised, so nothing on the device still reads the old bytes)
-        HIP_TRY(h, hipMemcpy(base + off_meta, meta.data(), meta.size(), hipMemcpyHostToDevice));
-        h->train_meta = meta;
+    char* base = nullptr;
+    {
+        const kanode_status r = train_buf_stage(h, off_meta, meta, st, base);
+        if (r != KANODE_OK) return r;
     }
     const double* md = (const double*)(base + off_meta);
     a->saveat = md;
@@ -1817,6 +1831,37 @@ int kanode_internal_pair_adjoint_workgroups(const kanode_handle* h, int64_t batc
 bool kanode_internal_fsens_ok(const kanode_handle* h, int64_t batch) {
     return h->spec.rhs_kind == KANODE_RHS_POINTWISE_PERIODIC_LAPLACIAN && h->spec.dtype == KANODE_F64 &&
            kan::fk_small_fsens_supported(h->hlc[0], (int)h->spec.nx, batch, h->fsens_wide);
+}
+bool kanode_internal_fk_train_ok(const kanode_handle* h, int64_t batch, bool with_test) {
+    if (!kanode_internal_fsens_ok(h, batch) || (with_test && !fk_small_ok(h, batch))) return false;
+    return kan::fk_small_train_supported(h->hlc[0], h->hpc, h->pp_on && h->hpc.enabled, (int)h->spec.nx, batch,
+                                         h->fsens_wide, with_test);
+}
+kanode_status kanode_internal_fk_train(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
+                                       const std::vector<char>& meta, int64_t res[2], void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t off_acc = 64;   // the accumulators of the two-entries-per-lane kernel (ChainTrainArgs::rec)
+    const size_t off_meta = off_acc + sizeof(double) * (size_t)kan::kFsensMaxWaves * 2 * 64;
+    char* base = nullptr;
+    {
+        const kanode_status r = train_buf_stage(h, off_meta, meta, st, base);
+        if (r != KANODE_OK) return r;
+    }
+    const double* md = (const double*)(base + off_meta);
+    a->saveat = md;
+    a->saveat_test = md + a->n_save;
+    a->rec = (double*)(base + off_acc);
+    a->out = (int64_t*)base;
+    const bool tab = h->pp_on && h->hpc.enabled;
+    const hipError_t e = kan::launch_fk_small_train(h->hlc[0], h->hpc, tab, h->dlc, h->dpc, fk_small_args(h), batch, *a,
+                                                    h->fsens_wide, st);
+    if (e == hipErrorNotSupported)
+        return fail(h, KANODE_ERR_UNSUPPORTED, "kanode_train_forward_tsit5: not supported (shape or saveat lists not "
+                                               "covered by the one-workgroup training kernel)");
+    if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_fk_small_train: ") + hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(res, a->out, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return KANODE_OK;
 }
 kanode_status kanode_internal_fk_fsens(kanode_handle* h, const void* p, const void* u0, int64_t batch,
                                        const kan::ChainSolveArgs* a, void* s_save, void* stream) {

@@ -139,6 +139,14 @@ bool kanode_internal_chain_adjoint_step_ok(const kanode_handle* h);
 bool kanode_internal_fsens_ok(const kanode_handle* h, int64_t batch);
 kanode_status kanode_internal_fk_fsens(kanode_handle* h, const void* p, const void* u0, int64_t batch,
                                        const kan::ChainSolveArgs* a, void* s_save, void* stream);
+// the device-resident Fisher-KPP training loop on the forward-mode gradient (fk_small_train_kernel,
+// kanode_train_forward_tsit5): whether the handle takes it at this batch (with_test: with the logged-loss solve),
+// and one launch.  meta = saveat [n_save] | saveat_test [n_save_test] (doubles), kept on the handle with the two
+// result words as kanode_internal_chain_train keeps its own; a's pointers to them are set here.  Synchronises;
+// res = iterations done, stop reason.
+bool kanode_internal_fk_train_ok(const kanode_handle* h, int64_t batch, bool with_test);
+kanode_status kanode_internal_fk_train(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
+                                       const std::vector<char>& meta, int64_t res[2], void* stream);
 void kanode_internal_clear_adjoint_steps(kanode_handle* h);
 std::vector<double>* kanode_internal_adjoint_steps(kanode_handle* h);
 kanode_status kanode_internal_pair_adjoint(kanode_handle* h, const void* p, int64_t batch, kan::PairAdjArgs* a,

@@ -2260,7 +2260,9 @@ extern "C" int32_t kanode_train_supported(const kanode_handle* h, int64_t batch)
     return h && batch >= 1 && kanode_internal_chain_train_ok(h, batch) ? 1 : 0;
 }
 
-extern "C" kanode_status kanode_train_tsit5(kanode_handle* h, void* p, void* m, void* v, const void* u0, int64_t batch,
+// The two device-resident loops share everything but the kernel: `forward` = the Fisher-KPP loop on the forward-mode
+// gradient (kanode_train_forward_tsit5), else the Lotka-Volterra loop on the InterpolatingAdjoint (kanode_train_tsit5).
+static kanode_status train_tsit5_impl(bool forward, kanode_handle* h, void* p, void* m, void* v, const void* u0, int64_t batch,
                                             double t0, double tf, const double* saveat, int64_t n_save,
                                             const void* target, double tf_test, const double* saveat_test,
                                             int64_t n_save_test, const void* target_test,
@@ -2273,32 +2275,42 @@ extern "C" kanode_status kanode_train_tsit5(kanode_handle* h, void* p, void* m, 
     if (stop_reason) *stop_reason = KANODE_TRAIN_OK;
     const kanode_solver_options o = resolved(opt);
     SOLVE_TRY(check_opts(h, o));
-    if (batch < 1 || !kanode_internal_chain_train_ok(h, batch))
+    const std::string name = forward ? "kanode_train_forward_tsit5" : "kanode_train_tsit5";
+    if (!forward && (batch < 1 || !kanode_internal_chain_train_ok(h, batch)))
         return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
                                     "kanode_train_tsit5: not supported (covered: one trajectory of an fp64 chain [2,10,2], "
                                     "G = 5, rbf, base activations, tanh_fast / softsign, fused_solve and chain_wide on)");
+    if (forward && (batch < 1 || !kanode_internal_fk_train_ok(h, batch, false)))
+        return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
+                                    "kanode_train_forward_tsit5: not supported (covered: the shapes of "
+                                    "kanode_forward_sensitivity_tsit5)");
+    if (forward && n_save_test > 0 && !kanode_internal_fk_train_ok(h, batch, true))
+        return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
+                                    "kanode_train_forward_tsit5: not supported (the test problem needs the one-workgroup "
+                                    "plain solve: even nx <= 64, the table path and fused_solve on, batch <= G + 2)");
     if (!p || !m || !v || !u0 || !target || !loss || !saveat || n_save < 1 || n_iters < 1 || !(tf > t0) || !iters_done ||
         !stop_reason)
-        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "kanode_train_tsit5: null pointer, n_save < 1, n_iters < 1 or tf <= t0");
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": null pointer, n_save < 1, n_iters < 1 or tf <= t0");
     if (n_save_test < 0 || (n_save_test > 0 && (!saveat_test || !target_test || !loss_test || !(tf_test > t0))))
-        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "kanode_train_tsit5: test problem needs saveat_test, target_test, loss_test and tf_test > t0");
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": test problem needs saveat_test, target_test, loss_test and tf_test > t0");
     // 1 - β^t must stay positive: the bias corrections divide by it (kanode_adam_step's condition)
     if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && beta1_t < 1.0 && beta2_t < 1.0))
-        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "kanode_train_tsit5: Adam needs 0 <= beta < 1 and beta_t < 1");
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": Adam needs 0 <= beta < 1 and beta_t < 1");
     auto check_saveat = [&](const double* sv, int64_t n, double te) -> bool {
         for (int64_t j = 1; j < n; ++j)
             if (!(sv[j] >= sv[j - 1])) return false;
         return n == 0 || (sv[0] >= t0 - 1e-12 * std::max(1.0, std::fabs(t0)) && sv[n - 1] <= te + 1e-12 * std::max(1.0, std::fabs(te)));
     };
     if (!check_saveat(saveat, n_save, tf) || !check_saveat(saveat_test, n_save_test, tf_test))
-        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "kanode_train_tsit5: saveat must ascend within [t0, tf]");
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": saveat must ascend within [t0, tf]");
     hipStream_t st = (hipStream_t)stream;
-    if (capturing(st)) return kanode_internal_fail(h, KANODE_ERR_CAPTURE, "kanode_train_tsit5 reads its status words");
+    if (capturing(st)) return kanode_internal_fail(h, KANODE_ERR_CAPTURE, name + " reads its status words");
     // the adjoint's stops and jump groups (those of kanode_adjoint_tsit5 for this saveat)
     std::vector<double> stops;
     std::vector<int32_t> rows, off;
-    adjoint_jump_groups(t0, tf, std::vector<double>(saveat, saveat + n_save), true, stops, rows, off);
+    if (!forward) adjoint_jump_groups(t0, tf, std::vector<double>(saveat, saveat + n_save), true, stops, rows, off);
     const int64_t ns = (int64_t)stops.size();
+    // (the forward loop's meta is the two saveat lists alone)
     std::vector<char> meta((size_t)(n_save + n_save_test + ns) * sizeof(double) + (off.size() + rows.size()) * sizeof(int32_t));
     {
         char* w = meta.data();
@@ -2353,7 +2365,8 @@ extern "C" kanode_status kanode_train_tsit5(kanode_handle* h, void* p, void* m, 
     a.p_before = (double*)p_before;
     a.counts = counts;
     int64_t res[2] = {0, 0};
-    SOLVE_TRY(kanode_internal_chain_train(h, &a, meta, res, st));
+    if (forward) SOLVE_TRY(kanode_internal_fk_train(h, batch, &a, meta, res, st));
+    else SOLVE_TRY(kanode_internal_chain_train(h, &a, meta, res, st));
     *iters_done = res[0];
     *stop_reason = (int32_t)res[1];
     if (res[1] != KANODE_TRAIN_OK) {
@@ -2361,10 +2374,42 @@ extern "C" kanode_status kanode_train_tsit5(kanode_handle* h, void* p, void* m, 
                                           "(KANODE_OPT_FUSED_SOLVE_CAP)", "adjoint Tsit5: maxiters reached",
                                           "loss is not finite", "test-loss Tsit5: maxiters reached"};
         const int64_t r = res[1] >= 1 && res[1] <= 5 ? res[1] : 0;
-        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, "kanode_train_tsit5: stopped at iteration " +
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": stopped at iteration " +
                                                                    std::to_string(res[0]) + ": " + why[r]);
     }
     return KANODE_OK;
+}
+
+extern "C" kanode_status kanode_train_tsit5(kanode_handle* h, void* p, void* m, void* v, const void* u0, int64_t batch,
+                                            double t0, double tf, const double* saveat, int64_t n_save,
+                                            const void* target, double tf_test, const double* saveat_test,
+                                            int64_t n_save_test, const void* target_test,
+                                            const kanode_solver_options* opt, double eta, double beta1, double beta2,
+                                            double eps, double beta1_t, double beta2_t, int64_t n_iters, double* loss,
+                                            double* loss_test, void* grad, void* p_before, int64_t* counts,
+                                            int64_t* iters_done, int32_t* stop_reason, void* stream) {
+    return train_tsit5_impl(false, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+                            n_save_test, target_test, opt, eta, beta1, beta2, eps, beta1_t, beta2_t, n_iters, loss,
+                            loss_test, grad, p_before, counts, iters_done, stop_reason, stream);
+}
+
+// ---- the device-resident Fisher-KPP loop on the forward-mode gradient (fk_small_train_kernel) ----
+extern "C" int32_t kanode_train_forward_supported(const kanode_handle* h, int64_t batch, int32_t with_test) {
+    return h && batch >= 1 && kanode_internal_fk_train_ok(h, batch, with_test != 0) ? 1 : 0;
+}
+
+extern "C" kanode_status kanode_train_forward_tsit5(kanode_handle* h, void* p, void* m, void* v, const void* u0,
+                                                    int64_t batch, double t0, double tf, const double* saveat,
+                                                    int64_t n_save, const void* target, double tf_test,
+                                                    const double* saveat_test, int64_t n_save_test,
+                                                    const void* target_test, const kanode_solver_options* opt,
+                                                    double eta, double beta1, double beta2, double eps, double beta1_t,
+                                                    double beta2_t, int64_t n_iters, double* loss, double* loss_test,
+                                                    void* grad, void* p_before, int64_t* counts, int64_t* iters_done,
+                                                    int32_t* stop_reason, void* stream) {
+    return train_tsit5_impl(true, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+                            n_save_test, target_test, opt, eta, beta1, beta2, eps, beta1_t, beta2_t, n_iters, loss,
+                            loss_test, grad, p_before, counts, iters_done, stop_reason, stream);
 }
 
 extern "C" kanode_status kanode_adjoint_tsit5(kanode_handle* h, const void* p, const kanode_solution* dense,

@@ -158,6 +158,12 @@ SIGNATURES = [
                                      C.POINTER(SolverOptsC), C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_double, C.c_double, C.c_int64, _P, _P, _P, _P, _P,
                                      C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P]),
+    ("kanode_train_forward_supported", C.c_int32, [_H, C.c_int64, C.c_int32]),
+    ("kanode_train_forward_tsit5", C.c_int, [_H, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double,
+                                             C.POINTER(C.c_double), C.c_int64, _P, C.c_double, C.POINTER(C.c_double),
+                                             C.c_int64, _P, C.POINTER(SolverOptsC), C.c_double, C.c_double, C.c_double,
+                                             C.c_double, C.c_double, C.c_double, C.c_int64, _P, _P, _P, _P, _P,
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P]),
     ("kanode_comm_unique_id", C.c_int, [_P]),
     ("kanode_comm_create", C.c_int, [C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(_P)]),
     ("kanode_comm_allreduce_sum", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),

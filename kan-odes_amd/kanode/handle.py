@@ -383,6 +383,20 @@ class KanodeHandle:
         """kanode_train_supported: the device-resident training loop covers this handle at `batch` trajectories."""
         return bool(L.lib().kanode_train_supported(self._h, int(batch)))
 
+    def train_forward_supported(self, batch: int, with_test: bool = False) -> bool:
+        """kanode_train_forward_supported: the device-resident Fisher-KPP loop on the forward-mode gradient covers this
+        handle at `batch` trajectories (with_test: with the logged-loss solve as well)."""
+        return bool(L.lib().kanode_train_forward_supported(self._h, int(batch), 1 if with_test else 0))
+
+    def train_forward_tsit5(self, p, m, v, u0, t0: float, tf: float, saveat, target, opts: "L.SolverOptsC",
+                            eta: float, beta, eps: float, beta_t, n_iters: int, test=None, record: bool = False):
+        """train_tsit5 for a small Fisher-KPP field (kanode_train_forward_tsit5: the gradient by forward
+        sensitivities): the same arguments and the same dict.  counts[:, :2] are the sensitivity solve's naccept and
+        nreject; counts[:, 2:] those of the iteration's logged-loss solve when a test problem is given, else zero
+        (there is no adjoint)."""
+        return self._train("kanode_train_forward_tsit5", p, m, v, u0, t0, tf, saveat, target, opts, eta, beta, eps,
+                           beta_t, n_iters, test, record)
+
     def train_tsit5(self, p, m, v, u0, t0: float, tf: float, saveat, target, opts: "L.SolverOptsC", eta: float,
                     beta, eps: float, beta_t, n_iters: int, test=None, record: bool = False):
         """n_iters whole training iterations in one launch (kanode_train_tsit5): p, m, v are updated in place.
@@ -391,6 +405,11 @@ class KanodeHandle:
         _lib.TRAIN_STOP name), error (the library's message when the loop stopped early, else None).  loss[it] is
         the loss at p_it, before the update; loss_test[it] at p_{it+1}.  An unsupported shape or a bad argument
         raises KanodeError; a stopped loop does not (the caller reads iters_done)."""
+        return self._train("kanode_train_tsit5", p, m, v, u0, t0, tf, saveat, target, opts, eta, beta, eps, beta_t,
+                           n_iters, test, record)
+
+    def _train(self, name, p, m, v, u0, t0, tf, saveat, target, opts, eta, beta, eps, beta_t, n_iters, test, record):
+        """The call of train_tsit5 / train_forward_tsit5 (the two entries share their signature)."""
         B = u0.shape[0] if u0.dim() == 2 else 1
         for t, nm in ((p, "p"), (m, "m"), (v, "v")):
             self._check_t(t, (self.P,), nm)
@@ -411,16 +430,16 @@ class KanodeHandle:
         pb = torch.zeros((n, self.P), **kw) if record else None
         counts = torch.zeros((n, 4), dtype=torch.int64, device=self.device) if record else None
         done, stop = C.c_int64(0), C.c_int32(0)
-        st = L.lib().kanode_train_tsit5(self._h, _ptr(p), _ptr(m), _ptr(v), _ptr(u0), B, float(t0), float(tf),
-                                        self._saveat_c(saveat), len(saveat), _ptr(target), float(tf_t), sv_t, n_t,
-                                        _ptr(tg_t), C.byref(opts), float(eta), float(beta[0]), float(beta[1]),
-                                        float(eps), float(beta_t[0]), float(beta_t[1]), n, _ptr(loss), _ptr(loss_t),
-                                        _ptr(grad), _ptr(pb), _ptr(counts), C.byref(done), C.byref(stop),
-                                        _stream(self.device))
+        st = getattr(L.lib(), name)(self._h, _ptr(p), _ptr(m), _ptr(v), _ptr(u0), B, float(t0), float(tf),
+                                    self._saveat_c(saveat), len(saveat), _ptr(target), float(tf_t), sv_t, n_t,
+                                    _ptr(tg_t), C.byref(opts), float(eta), float(beta[0]), float(beta[1]),
+                                    float(eps), float(beta_t[0]), float(beta_t[1]), n, _ptr(loss), _ptr(loss_t),
+                                    _ptr(grad), _ptr(pb), _ptr(counts), C.byref(done), C.byref(stop),
+                                    _stream(self.device))
         err = None
         if st != L.OK:
             if stop.value == 0:
-                L.check(st, self._h, "kanode_train_tsit5")
+                L.check(st, self._h, name)
             err = L.lib().kanode_last_error(self._h).decode()
         return dict(loss=loss, loss_test=loss_t, grad=grad, p_before=pb, counts=counts, iters_done=int(done.value),
                     stop=L.TRAIN_STOP.get(int(stop.value), str(stop.value)), error=err)

@@ -159,6 +159,7 @@ class Trainer:
             sensealg = ("auto" if getattr(rhs, "auto_sensealg", False) else "interpolating_adjoint") \
                 if hasattr(rhs, "vjp_stage") else "discrete"
         self.sensealg = sensealg
+        self.last_run = None  # the loop the last run() took: "device_forward", "device_adjoint" or "host"
         self._pver = 0        # bumped by every optimiser update (keys the cached forward of eval_loss)
         self._pre = None      # (pver, path, forward payload) from eval_loss, consumed by the next step
 
@@ -257,20 +258,27 @@ class Trainer:
         self.history.append(lv)
         return lv, g_own, sol
 
-    def _native_run_ok(self) -> bool:
-        """Whether run() takes the device-resident loop (kanode_train_tsit5): the handle covers the shape, the
-        gradient is the plain-MSE InterpolatingAdjoint of this rank alone, and the optimiser is FusedAdam."""
+    def _native_run_path(self, with_test: bool = False):
+        """The device-resident loop run() takes, or None: "device_adjoint" (kanode_train_tsit5: the plain-MSE
+        InterpolatingAdjoint) or "device_forward" (kanode_train_forward_tsit5: the plain-MSE forward-mode gradient
+        of a small Fisher-KPP field, with_test: with its logged-loss solve), where the handle covers the shape, the
+        gradient is this rank's alone and the optimiser is FusedAdam."""
         hd = getattr(self.rhs, "hd", None)
-        if (hd is None or self.sensealg != "interpolating_adjoint" or self.group is not None or self.tp
-                or self.sparse_reg or type(self.opt) is not FusedAdam or not self.p.is_cuda):
-            return False
+        if (hd is None or self.sensealg not in ("interpolating_adjoint", "forward", "auto") or self.group is not None
+                or self.tp or self.sparse_reg or type(self.opt) is not FusedAdam or not self.p.is_cuda):
+            return None
         if self.p.dtype != torch.float64 or not (self.p.is_contiguous() and self.u0.is_contiguous()):
-            return False
+            return None
         if self.solver.control != "auto" or self.solver.replay_dts is not None \
                 or self.solver.replay_adjoint_dts is not None:
-            return False                                  # (host / hipGraph step control, replayed steps: step())
+            return None                                   # (host / hipGraph step control, replayed steps: step())
         B = self.u0.shape[0] if self.u0.dim() == 2 else 1
-        return self._fast_path()[1] == "interpolating_adjoint" and hd.train_supported(B)
+        path = self._fast_path()[1]                       # ("auto" resolved; it turns fsens_wide on where it applies)
+        if path == "interpolating_adjoint" and self.sensealg == "interpolating_adjoint" and hd.train_supported(B):
+            return "device_adjoint"
+        if path == "forward" and hd.train_forward_supported(B, with_test):
+            return "device_forward"
+        return None
 
     def run(self, n_iters: int, test=None, chunk: int = 256, record: bool = False) -> dict:
         """n_iters iterations of the driver loop (LV_driver_KANODE.jl:279-291): step(), and with
@@ -280,8 +288,11 @@ class Trainer:
         "p_before" ([n_iters, P], on p's device) and "counts" ([n_iters, 4] int64, CPU: forward naccept, nreject,
         adjoint naccept, nreject).
 
-        Where the handle covers it (one Lotka-Volterra trajectory, fp64, plain MSE, FusedAdam, no group) the
-        iterations run on the device, at most `chunk` per kernel launch (no single kernel runs for long on a shared
+        Where the handle covers it (one Lotka-Volterra trajectory on the InterpolatingAdjoint, or a small Fisher-KPP
+        field on the forward-mode gradient -- explicitly or through "auto" --; fp64, plain MSE, FusedAdam, no group)
+        the iterations run on the device (self.last_run says which loop ran: "device_adjoint", "device_forward" or
+        "host"; on the forward loop there is no adjoint, and counts[:, 2:] are the logged-loss solve's naccept and nreject
+        when a test problem is given, else zero), at most `chunk` per kernel launch (no single kernel runs for long on a shared
         machine): the optimiser's own m, v and running powers are used and advanced.  If the device loop stops (a
         solve at maxiters, the dense-output capacity, a non-finite loss) the iterations before it are kept in
         history and a KanodeError names the iteration and reason, p, m, v as the last good iteration left them.
@@ -294,11 +305,13 @@ class Trainer:
             tspan_t, saveat_t, target_t = test
             sv_t = _saveat_list(tspan_t, saveat_t)
             sv_t = [s for s in sv_t if s <= float(tspan_t[1]) + 1e-12 * max(1.0, abs(float(tspan_t[1])))]
-        if n_iters > 0 and self._native_run_ok() and (
-                test is None or (float(tspan_t[0]) == float(self.tspan[0])
-                                 and tuple(target_t.shape) == (len(sv_t),) + tuple(self.u0.shape))):
+        dev = self._native_run_path(test is not None) if n_iters > 0 else None
+        if dev is not None and (test is None or (float(tspan_t[0]) == float(self.tspan[0])
+                                                 and tuple(target_t.shape) == (len(sv_t),) + tuple(self.u0.shape))):
+            self.last_run = dev
             return self._run_native(n_iters, None if test is None else (float(tspan_t[1]), sv_t, target_t),
-                                    int(chunk), record)
+                                    int(chunk), record, forward=dev == "device_forward")
+        self.last_run = "host"
         loss, loss_t, grads, pbs, counts = [], [], [], [], []
         for _ in range(n_iters):
             if record:
@@ -324,7 +337,7 @@ class Trainer:
             out["counts"] = torch.tensor(counts, dtype=torch.int64).reshape(len(counts), 4)
         return out
 
-    def _run_native(self, n_iters: int, test, chunk: int, record: bool) -> dict:
+    def _run_native(self, n_iters: int, test, chunk: int, record: bool, forward: bool = False) -> dict:
         from . import _lib as L
         hd = self.rhs.hd
         self._drop_pre()
@@ -342,8 +355,9 @@ class Trainer:
         parts, left, err = [], n_iters, None
         while left > 0 and err is None:
             k = min(left, chunk)
-            r = hd.train_tsit5(self.p, mt, vt, self.u0, float(self.tspan[0]), float(self.tspan[1]), sv, target, oc,
-                               self.opt.eta, (b1, b2), self.opt.eps, bp, k, test=test, record=record)
+            call = hd.train_forward_tsit5 if forward else hd.train_tsit5
+            r = call(self.p, mt, vt, self.u0, float(self.tspan[0]), float(self.tspan[1]), sv, target, oc,
+                     self.opt.eta, (b1, b2), self.opt.eps, bp, k, test=test, record=record)
             d = r["iters_done"]
             for _ in range(d):                            # Flux's βp .*= β, once per iteration done
                 bp[0] *= b1
