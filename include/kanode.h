@@ -26,6 +26,8 @@
  *       the RHS pullback SciMLSensitivity requests per adjoint stage (λᵀ∂f/∂u, λᵀ∂f/∂p)
  *   kanode_edge_activations
  *       per-edge activations                                 Lotka-Volterra/Activation_getter.jl:3-63
+ *   kanode_edge_scores
+ *       max_k |activation| per edge: prune's scores          Lotka-Volterra/LV_driver_KANODE.jl:79-80
  *
  * Layout: the reference's Julia column-major arrays.  A state / layer input is
  * [N, B] with element (n, b) at n + N*b (one trajectory contiguous).  The flat
@@ -442,7 +444,16 @@ kanode_status kanode_adam_step(void* x, void* m, void* v, const void* g, int64_t
  * A failing iteration stops the loop BEFORE its Adam step, p, m, v left as the last good iteration made them:
  * *iters_done (host) = the iterations completed, *stop_reason (host) = a kanode_train_stop.  The call synchronises
  * the stream; it returns KANODE_OK with *iters_done = n_iters, or KANODE_ERR_INVALID_ARG with the iteration and
- * reason in kanode_last_error.  A capturing stream is refused (KANODE_ERR_CAPTURE). */
+ * reason in kanode_last_error.  A capturing stream is refused (KANODE_ERR_CAPTURE).
+ *
+ * The sparsity term (the driver's sparse_on = 1: loss(p) + reg_loss(p, 5e-4, 0), LV_driver_KANODE.jl:187-201):
+ * with a penalty weight λ = kanode_get_l1_penalty(h) > 0, read when the call is issued,
+ *     loss[it] = mean((u_save - target)²) + λ·Σ_q |p_q|      (one rounded product, one rounded sum; the stop test
+ *                                                              reads this value)
+ *     dp_q     = InterpolatingAdjoint's dp_q + λ·sgn(p_q)     (sgn(0) = 0; what Adam and the grad record receive)
+ * loss_test, the adjoint and the counts are as without it.  A parameter that is exactly zero makes the loss NaN,
+ * as the host formula is there (its entropy term is 0·log 0 at any weight): KANODE_TRAIN_LOSS_NOT_FINITE.  With
+ * λ = 0 (the default) no operation is added and every result keeps its bits. */
 typedef enum {
     KANODE_TRAIN_OK = 0,
     KANODE_TRAIN_FORWARD_MAXITERS = 1,   /* the forward solve reached opt->maxiters */
@@ -452,6 +463,11 @@ typedef enum {
     KANODE_TRAIN_TEST_MAXITERS = 5       /* the test-loss solve reached opt->maxiters (its iteration's update is kept) */
 } kanode_train_stop;
 int32_t kanode_train_supported(const kanode_handle* h, int64_t batch);
+/* λ of the L1 term above: finite and >= 0 (else KANODE_ERR_INVALID_ARG), default 0.  Only kanode_train_tsit5
+ * computes a loss with it; kanode_train_forward_tsit5 refuses a non-zero penalty (KANODE_ERR_UNSUPPORTED, nothing
+ * launched) and every other entry point ignores it. */
+kanode_status kanode_set_l1_penalty(kanode_handle* h, double act_reg);
+double kanode_get_l1_penalty(const kanode_handle* h);
 kanode_status kanode_train_tsit5(kanode_handle* h, void* p, void* m, void* v, const void* u0, int64_t batch,
                                  double t0, double tf, const double* saveat, int64_t n_save, const void* target,
                                  double tf_test, const double* saveat_test, int64_t n_save_test,
@@ -540,6 +556,14 @@ kanode_status kanode_layer_vjp(kanode_handle* h, int32_t layer, const void* p_la
  * (Σ_i act(o,i,k) == y(o,k): the Activation_getter.jl:33-36,55-61 identity) */
 kanode_status kanode_edge_activations(kanode_handle* h, int32_t layer, const void* p_layer, const void* x,
                                       void* act, int64_t K, void* stream);
+/* scores[O, I] with scores(o,i) = max_k |act(o,i,k)|, act as kanode_edge_activations defines it: the per-edge
+ * quantity the reference's prune reads from activation_getter (LV_driver_KANODE.jl:79-80), formed without the
+ * [O, I, K] array and for every layer the handle accepts (any out_dims).  Each activation is computed by
+ * kanode_edge_activations' arithmetic, so for out_dims <= 64 the scores are the maxima of its output bit for bit.
+ * A NaN activation makes its edge's score NaN (the maximum does not drop it).  K <= 0: KANODE_ERR_INVALID_ARG.
+ * Stream-ordered; uses the handle's partial-row workspace (no atomics: per-block maxima, then one reduction). */
+kanode_status kanode_edge_scores(kanode_handle* h, int32_t layer, const void* p_layer, const void* x, void* scores,
+                                 int64_t K, void* stream);
 
 #ifdef __cplusplus
 }

@@ -440,29 +440,41 @@ end
 # and the outputs are device pointers (upload / DevBuf); saveat lists are host vectors.  βp: Flux's running powers
 # (opt.state[p][3]) on entry; advance them by the returned iteration count afterwards.
 train_supported(h::Handle, B::Integer) = ccall(sym(:kanode_train_supported), Int32, (Ptr{Cvoid}, Int64), h.ptr, B) == 1
+# λ of kanode_train_tsit5's L1 term (finite, >= 0; 0 = plain MSE).  kanode_train_forward_tsit5 refuses a non-zero one.
+set_l1_penalty!(h::Handle, λ::Real) = check(h, ccall(sym(:kanode_set_l1_penalty), Cint, (Ptr{Cvoid}, Float64), h.ptr, λ))
+l1_penalty(h::Handle) = ccall(sym(:kanode_get_l1_penalty), Float64, (Ptr{Cvoid},), h.ptr)
 
 """train_tsit5!(h, p, m, v, u0, tspan, saveat, target, n_iters, loss; η, β, ϵ, βp, test, loss_test, grad, p_before,
 counts, opt) -> (iters_done, stop_reason).  loss[it] is the loss at p_it (before the update), loss_test[it] at
 p_{it+1}; test = (tf_test, saveat_test, target_test).  A stopped loop (stop_reason != 0: a kanode_train_stop)
-returns normally with p, m, v as the last good iteration left them; any other failure throws."""
+returns normally with p, m, v as the last good iteration left them; any other failure throws.
+l1: the weight λ of the sparsity term of sparse_on = 1 (LV_driver_KANODE.jl:187-201: loss + λ·Σ|p|, gradient +
+λ·sign(p)), set on the handle for this call and restored afterwards."""
 function train_tsit5!(h::Handle, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cvoid}, u0::Ptr{Cvoid}, tspan,
                       saveat::Vector{Float64}, target::Ptr{Cvoid}, n_iters::Integer, loss::Ptr{Cvoid};
                       η::Real = 1e-3, β = (0.9, 0.999), ϵ::Real = 1e-8, βp = β, test = nothing,
                       loss_test::Ptr{Cvoid} = C_NULL, grad::Ptr{Cvoid} = C_NULL, p_before::Ptr{Cvoid} = C_NULL,
                       counts::Ptr{Cvoid} = C_NULL, opt::SolverOptions = default_options(),
-                      stream::Ptr{Cvoid} = C_NULL)
+                      stream::Ptr{Cvoid} = C_NULL, l1::Real = 0.0)
     train_supported(h, 1) || throw(ArgumentError("train_tsit5!: not covered for this handle"))
     issorted(saveat) || throw(ArgumentError("saveat must be ascending"))
     tf_t, sv_t, tg_t = test === nothing ? (0.0, Float64[], Ptr{Cvoid}(C_NULL)) : (Float64(test[1]), Vector{Float64}(test[2]), test[3])
     done = Ref{Int64}(0)
     stop = Ref{Int32}(0)
-    st = GC.@preserve saveat sv_t ccall(sym(:kanode_train_tsit5), Cint,
-        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float64}, Int64,
-         Ptr{Cvoid}, Float64, Ptr{Float64}, Int64, Ptr{Cvoid}, Ref{SolverOptions}, Float64, Float64, Float64, Float64,
-         Float64, Float64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64}, Ref{Int32},
-         Ptr{Cvoid}),
-        h.ptr, p, m, v, u0, 1, tspan[1], tspan[2], saveat, length(saveat), target, tf_t, sv_t, length(sv_t), tg_t,
-        opt, η, β[1], β[2], ϵ, βp[1], βp[2], n_iters, loss, loss_test, grad, p_before, counts, done, stop, stream)
+    old = l1_penalty(h)
+    set_l1_penalty!(h, l1)
+    local st
+    try
+        st = GC.@preserve saveat sv_t ccall(sym(:kanode_train_tsit5), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float64}, Int64,
+             Ptr{Cvoid}, Float64, Ptr{Float64}, Int64, Ptr{Cvoid}, Ref{SolverOptions}, Float64, Float64, Float64,
+             Float64, Float64, Float64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64},
+             Ref{Int32}, Ptr{Cvoid}),
+            h.ptr, p, m, v, u0, 1, tspan[1], tspan[2], saveat, length(saveat), target, tf_t, sv_t, length(sv_t), tg_t,
+            opt, η, β[1], β[2], ϵ, βp[1], βp[2], n_iters, loss, loss_test, grad, p_before, counts, done, stop, stream)
+    finally
+        set_l1_penalty!(h, old)
+    end
     stop[] == 0 && check(h, st)
     return done[], stop[]
 end
@@ -500,6 +512,87 @@ function train_forward_tsit5!(h::Handle, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cv
         opt, η, β[1], β[2], ϵ, βp[1], βp[2], n_iters, loss, loss_test, grad, p_before, counts, done, stop, stream)
     stop[] == 0 && check(h, st)
     return done[], stop[]
+end
+
+# --- pruning a sparsified KAN (LV_driver_KANODE.jl:52-108): per-edge scores on the device, the keep rule and the
+# parameter slicing on the host.  Scores are Julia [O, I] matrices (the memory kanode_edge_scores writes).
+layer_length(h::Handle, i::Integer) = Int(ccall(sym(:kanode_layer_param_length), Int64, (Ptr{Cvoid}, Int32), h.ptr, i))
+
+"""edge_scores(l, x, p) -> [scores_1, scores_2, ..]: scores_i[o, j] = max_k |φ_{o,j}(x_k)| of layer i, x [I, K]
+propagated through the layers with kanode_layer_forward (Activation_getter.jl:39).  The quantity prune reads from
+activation_getter (:79-80), without the per-sample arrays; a NaN activation makes its edge's score NaN."""
+function edge_scores(l::KANChainHip, x::AbstractMatrix, p::AbstractVector)
+    h = l.h
+    checkp(h, p)
+    checku(h, x, h.nin, "x")
+    T = h.T
+    K = size(x, 2)
+    K >= 1 || throw(ArgumentError("edge_scores needs at least one sample"))
+    pd, xd = upload(tohost(T, p)), upload(tohost(T, x))
+    out = Matrix{T}[]
+    off = 0
+    sig = (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid})
+    for (i, s) in enumerate(l.specs)
+        sc = Matrix{T}(undef, Int(s.out_dims), Int(s.in_dims))
+        sd = DevBuf(sizeof(sc))
+        pl = pd.ptr + off * sizeof(T)
+        GC.@preserve pd xd sd check(h, ccall(sym(:kanode_edge_scores), Cint, sig, h.ptr, i - 1, pl, xd.ptr, sd.ptr, K,
+                                             C_NULL))
+        push!(out, download!(sc, sd))
+        if i < length(l.specs)
+            yd = DevBuf(Int(s.out_dims) * K * sizeof(T))
+            GC.@preserve pd xd yd check(h, ccall(sym(:kanode_layer_forward), Cint, sig, h.ptr, i - 1, pl, xd.ptr,
+                                                 yd.ptr, K, C_NULL))
+            hipcheck(ccall((:hipDeviceSynchronize, HIPLIB), Cint, ()), "hipDeviceSynchronize")
+            xd = yd
+        end
+        off += layer_length(h, i - 1)
+    end
+    return out
+end
+
+"""prune_nodes(scores, θ) -> kept: for every hidden layer the nodes j with
+min(max_i scores_l[j, i], max_o scores_{l+1}[o, j]) > θ (:79-83), all scores taken on the unpruned network."""
+function prune_nodes(scores::AbstractVector, θ::Real)
+    length(scores) >= 2 || throw(ArgumentError("prune needs a chain of at least 2 layers"))
+    all(s -> all(isfinite, s), scores) || throw(ArgumentError("prune: a score is not finite"))
+    kept = Vector{Int}[]
+    for l in 1:(length(scores) - 1)
+        in_score = vec(maximum(scores[l]; dims = 2))
+        out_score = vec(maximum(scores[l + 1]; dims = 1))
+        k = findall(min.(in_score, out_score) .> θ)
+        isempty(k) && throw(ArgumentError("prune: every node of hidden layer $l scores at most θ"))
+        push!(kept, k)
+    end
+    return kept
+end
+
+"""prune(l, p, x; theta = 1e-2) -> (l_pruned, p_pruned, kept): the narrower chain and its flat parameters.  Layer i
+keeps the rows kept[i] of C and W, layer i + 1 the column blocks g + G·(j - 1) of C and the columns j of W for j in
+kept[i].  Unlike the reference's prune (which slices the freshly initialised global pM, :96-104, and fills layer 2's
+W from its C, :104) the kept nodes keep their trained C and W."""
+function prune(l::KANChainHip, p::AbstractVector, x::AbstractMatrix; theta::Real = 1e-2, device::Integer = 0)
+    kept = prune_nodes(edge_scores(l, x, p), theta)
+    specs, pp = LayerSpec[], eltype(p)[]
+    off = 0
+    n = length(l.specs)
+    for (i, s) in enumerate(l.specs)
+        I, O, G = Int(s.in_dims), Int(s.out_dims), Int(s.grid_len)
+        rows = i < n ? kept[i] : collect(1:O)
+        ins = i > 1 ? kept[i - 1] : collect(1:I)
+        cols = vec([g + G * (j - 1) for g in 1:G, j in ins])
+        C = reshape(p[(off + 1):(off + O * G * I)], O, G * I)
+        off += O * G * I
+        append!(pp, vec(C[rows, cols]))
+        if s.use_base_act == 1
+            W = reshape(p[(off + 1):(off + O * I)], O, I)
+            off += O * I
+            append!(pp, vec(W[rows, ins]))
+        end
+        push!(specs, LayerSpec(Int32(length(ins)), Int32(length(rows)), s.grid_len, s.normalizer, s.basis,
+                               s.use_base_act, s.grid_lo, s.grid_hi, s.denominator, s.iqf_reference_quirk))
+    end
+    return KANChainHip(specs; T = l.h.T, device), pp, kept
 end
 
 # --- data-parallel training across GPUs (kanode_comm_*): one process per GPU, each with its trajectory

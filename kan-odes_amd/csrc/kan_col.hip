@@ -7,6 +7,7 @@
 // with rrule(_rbf) (utils.jl:15-21), per-edge activations Activation_getter.jl.
 // Parameter gradients: per-block LDS-staged tile products into a slab, then the
 // ordered slab reduction (bitwise reproducible; no float atomics).
+#include "kan_basis.hpp"
 #include "kan_common.hpp"
 #include "kan_kernels.hpp"
 #include "kan_onewg.hpp"
@@ -36,37 +37,6 @@ hipError_t launch_slab_reduce(const T* slab, int64_t nblk, int64_t P, T* dp, hip
     hipLaunchKernelGGL((slab_reduce_kernel<T>), dim3((unsigned)P), dim3(kBlock), 0, st, slab, nblk, P, dp);
     return hipGetLastError();
 }
-
-// Sequential basis generator for one normalised input: direct (per-knot formula)
-// or the Gaussian recurrence.
-template <typename T, int PATH>
-struct BasisStream {
-    T n, F, R, z0, tau, invh;
-    __device__ __forceinline__ void init(const Math<T>& M, const LayerConst& lc, T nn) {
-        n = nn;
-        invh = T(lc.invh);
-        if constexpr (PATH != PATH_DIRECT) rec_anchor<T>(M, lc, n, z0, F, R, tau);   // tau = τ - τ_c
-    }
-    // returns φ_g, z_g (the scaled argument), aux (tanh for rswaf)
-    __device__ __forceinline__ T next(const Math<T>& M, const LayerConst& lc, int g, T& z, T& aux) {
-        if constexpr (PATH == PATH_DIRECT) {
-            z = (n - T(lc.grid[g])) * invh;
-            aux = T(0);
-            return basis_direct<T>(M, lc.basis, z, aux);
-        } else {
-            T kc = T(lc.K[g]);
-            if constexpr (PATH == PATH_REC_CORR) {
-                const T e = T(lc.e[g]);
-                kc = kc * kfma<T>(tau, kfma<T>(tau, T(0.5) * e * e, e), T(1));
-            }
-            const T v = F * kc;
-            z = z0 - T(lc.Dl[g]);
-            aux = T(0);
-            F = F * R;
-            return v;
-        }
-    }
-};
 
 template <typename T, int NORM, int PATH, int OMAX>
 __global__ void __launch_bounds__(kBlock)

@@ -317,6 +317,12 @@ hipError_t launch_kd_vjp_col(const LayerConst& hlc, const LayerConst* lc, const 
 template <typename T>
 hipError_t launch_kd_edge_act(const LayerConst& hlc, const LayerConst* lc, const T* p, const T* x, T* act, int64_t K,
                               hipStream_t st);
+// scores[o + O·i] = max_k |act(o, i, k)| with act as launch_kd_edge_act forms it, any O, no [O, I, K] intermediate
+// (kan_score.hip); a NaN activation makes its edge's score NaN.  slab: slab_bytes of per-block maxima (the sample
+// range is split over as many blocks as it holds rows of O·I; none: one block per edge group visits every sample).
+template <typename T>
+hipError_t launch_kd_edge_scores(const LayerConst& hlc, const LayerConst* lc, const T* p, const T* x, T* scores,
+                                 T* slab, size_t slab_bytes, int64_t K, hipStream_t st);
 
 // device-side Tsit5 step control (kan_solve.hip; kanode_solve.cpp graph mode)
 struct SolveCtl {
@@ -498,6 +504,8 @@ struct ChainTrainArgs {
     int64_t* counts;               // [n_iters][4] or null: forward naccept/nreject, adjoint naccept/nreject (the
                                    // Fisher-KPP loop: the logged-loss solve's in place of the adjoint's)
     int64_t* out;                  // iters_done, ChainTrainStop
+    double act_reg;                // λ of the L1 term λ·Σ|p| in the loss (kd_chain_train_lvsp_kernel; 0: plain MSE).
+                                   // The Fisher-KPP loop has no such term and ignores it.
 };
 bool chain_train_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B, size_t esize, bool wide);
 // the dynamic LDS of a launch with these sizes, and whether the dense output of `cap` steps is staged in it;

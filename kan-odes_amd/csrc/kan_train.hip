@@ -10,13 +10,15 @@
 // One workgroup of (kLvSpWaves + 1) waves, as the lvsp adjoint.  Per iteration `it`:
 //   A  wave 0: the forward solve at p_it over (t0, tf) (onewg_tsit5 in its wave-local mode with ChainModel: the
 //      arithmetic of kd_chain_tsit5_kernel), the dense output into LDS (or global when cap steps do not fit),
-//      then loss[it] and dl = (u_save - X)·2/numel in place of u_save;
+//      then loss[it] (with a penalty weight λ = act_reg: + λ·Σ|p|, the driver's sparse_on = 1 loss) and
+//      dl = (u_save - X)·2/numel in place of u_save;
 //      wave 1, at the same time and at the same p_it: the test-loss solve over (t0, tf_test) -> loss_test[it-1]
 //      (the test solve of iteration it-1 is the solve at p_it = p_{(it-1)+1}; the last one runs alone after the
 //      loop).  Waves 2..6 wait at the barrier.
 //   -- barrier; every thread reads the solves' status words and stops the loop on a failure
 //   B  all waves: lvsp_adjoint (its own barriers: 2 per attempted step, + 2 for the initial step)
-//   C  wave 0: the optional records (counts, grad, p_before), then Adam on its μ entries (adam_entry: the
+//   C  wave 0: the gradient μ (+ λ·sgn(p) with a penalty), the optional records (counts, grad, p_before), then
+//      Adam on its entries (adam_entry: the
 //      statement of adam_step_kernel) -> p (global and the LDS copy), m, v
 //   -- barrier; βp1, βp2 advance by one product in every thread
 // so two barriers per iteration besides the adjoint's.
@@ -39,6 +41,25 @@ __device__ __forceinline__ double wave_mse(double* __restrict__ us, const double
         if constexpr (DL) us[i] = __dmul_rn(d, scale);
     }
     return __ddiv_rn(wave_sum(s), (double)cnt);
+}
+
+// mse + λ·Σ_q |ps[q]| over the calling wave (reg_loss(p, λ, 0), LV_driver_KANODE.jl:187-201), ps in LDS: the sum in
+// wave_mse's order (lane l adds its entries l, l + 64, .. ascending, then the wave butterfly), then one rounded
+// product and one rounded sum.  An entry that is exactly zero makes the loss NaN, as the host formula is there
+// (its entropy term is 0·log 0 even at weight 0): the loop then stops with kTrainLossNotFinite.
+__device__ __forceinline__ double l1_loss(double mse, const double* __restrict__ ps, int P, double lam) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & (kWave - 1);
+    double s = 0.0;
+    bool zero = false;
+    for (int q = lane; q < P; q += kWave) {
+        const double x = ps[q];
+        s = s + ::fabs(x);
+        zero = zero || x == 0.0;
+    }
+    const double A = wave_sum(s);
+    const double lv = mse + lam * A;
+    return __any(zero) ? __longlong_as_double(0x7ff8000000000000LL) : lv;
 }
 
 // NORM: the adjoint's normalizer; FN, PATH, FS: the forward's ChainModel specialisation (what
@@ -137,7 +158,8 @@ kd_chain_train_lvsp_kernel(const LayerConst* __restrict__ lcs, ChainTrainArgs a)
                 const double lt = wave_mse<false>(ust, a.target_test, a.n_save_test * N, 0.0);
                 if (lane == 0) a.loss_test[it - 1] = fo[1][3] == 0 ? lt : __longlong_as_double(0x7ff8000000000000LL);
             } else if (fo[0][3] == 0) {   // (lane 0's own store, read back by the wave)
-                const double lv = wave_mse<true>(dl, a.target, a.n_save * N, a.dl_scale);
+                double lv = wave_mse<true>(dl, a.target, a.n_save * N, a.dl_scale);
+                if (a.act_reg != 0.0) lv = l1_loss(lv, ps, P, a.act_reg);   // (λ = 0: not one operation more)
                 if (lane == 0) {
                     a.loss[it] = lv;
                     lossv = lv;
@@ -192,10 +214,13 @@ kd_chain_train_lvsp_kernel(const LayerConst* __restrict__ lcs, ChainTrainArgs a)
                 const int q = lane + kWave * r;
                 if (q < P) {
                     const double x = ps[q];
-                    if (a.grad) a.grad[it * P + q] = mu[r];
+                    double gq = mu[r];
+                    // ∂(λ·Σ|p|)/∂p_q = λ·sgn(p_q), sgn(0) = 0: one rounded add (λ = 0: none, a -0.0 stays -0.0)
+                    if (a.act_reg != 0.0) gq = __dadd_rn(gq, x > 0.0 ? a.act_reg : (x < 0.0 ? -a.act_reg : 0.0));
+                    if (a.grad) a.grad[it * P + q] = gq;
                     if (a.p_before) a.p_before[it * P + q] = x;
                     double mq = a.m[q], vq = a.v[q];
-                    const double xn = adam_entry<double>(x, mq, vq, mu[r], ad);
+                    const double xn = adam_entry<double>(x, mq, vq, gq, ad);
                     a.m[q] = mq;
                     a.v[q] = vq;
                     a.p[q] = xn;

@@ -73,6 +73,7 @@ struct kanode_handle {
     bool record_adj_steps = false;    // KANODE_OPT_RECORD_ADJOINT_STEPS
     bool fk_loop = true;              // KANODE_OPT_FK_DEVICE_LOOP
     int fsens_wide = 0;               // KANODE_OPT_FSENS_WIDE
+    double l1_penalty = 0.0;          // kanode_set_l1_penalty: λ of kanode_train_tsit5's loss term λ·Σ|p|
     std::vector<double> adj_steps;    // the last kanode_adjoint_tsit5's accepted step sizes (when recorded)
     bool adj_fused_finish = false;    // KANODE_OPT_ADJ_FUSED_FINISH (measured even with the finish launch)
     unsigned* fin_ctr = nullptr;      // its two arrival counters (device, zeroed at allocation)
@@ -1141,6 +1142,16 @@ int64_t kanode_get_option(const kanode_handle* h, int32_t option) {
     return -1;
 }
 
+kanode_status kanode_set_l1_penalty(kanode_handle* h, double act_reg) {
+    if (!h) return KANODE_ERR_INVALID_ARG;
+    if (!(act_reg >= 0.0) || !std::isfinite(act_reg))
+        return fail(h, KANODE_ERR_INVALID_ARG, "kanode_set_l1_penalty: act_reg must be finite and >= 0");
+    h->l1_penalty = act_reg;
+    return KANODE_OK;
+}
+
+double kanode_get_l1_penalty(const kanode_handle* h) { return h ? h->l1_penalty : 0.0; }
+
 kanode_status kanode_rhs(kanode_handle* h, const void* p, const void* u, void* du, int64_t batch, void* stream) {
     kanode_status s = check_handle(h);
     if (s != KANODE_OK) return s;
@@ -1318,6 +1329,27 @@ kanode_status kanode_edge_activations(kanode_handle* h, int32_t layer, const voi
     } else {
         HIP_TRY(h, kan::launch_kd_edge_act<float>(h->hlc[layer], h->dlc + layer, (const float*)p_layer - off,
                                                   (const float*)x, (float*)act, K, st));
+    }
+    return KANODE_OK;
+}
+
+kanode_status kanode_edge_scores(kanode_handle* h, int32_t layer, const void* p_layer, const void* x, void* scores,
+                                 int64_t K, void* stream) {
+    kanode_status s = check_handle(h);
+    if (s != KANODE_OK) return s;
+    if (layer < 0 || layer >= h->n_layers) return fail(h, KANODE_ERR_INVALID_ARG, "layer out of range");
+    if (K <= 0) return fail(h, KANODE_ERR_INVALID_ARG, "kanode_edge_scores: K <= 0 (a maximum over no samples)");
+    if (!p_layer || !x || !scores) return fail(h, KANODE_ERR_INVALID_ARG, "null pointer");
+    const int64_t off = h->hlc[layer].p_off;
+    hipStream_t st = (hipStream_t)stream;
+    if (h->spec.dtype == KANODE_F64) {
+        HIP_TRY(h, kan::launch_kd_edge_scores<double>(h->hlc[layer], h->dlc + layer, (const double*)p_layer - off,
+                                                      (const double*)x, (double*)scores, (double*)h->slab,
+                                                      h->slab_bytes, K, st));
+    } else {
+        HIP_TRY(h, kan::launch_kd_edge_scores<float>(h->hlc[layer], h->dlc + layer, (const float*)p_layer - off,
+                                                     (const float*)x, (float*)scores, (float*)h->slab, h->slab_bytes,
+                                                     K, st));
     }
     return KANODE_OK;
 }

@@ -2284,6 +2284,10 @@ static kanode_status train_tsit5_impl(bool forward, kanode_handle* h, void* p, v
         return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
                                     "kanode_train_forward_tsit5: not supported (covered: the shapes of "
                                     "kanode_forward_sensitivity_tsit5)");
+    if (forward && kanode_get_l1_penalty(h) != 0.0)
+        return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
+                                    "kanode_train_forward_tsit5: not supported (the L1 penalty of "
+                                    "kanode_set_l1_penalty is kanode_train_tsit5's alone; set it to 0)");
     if (forward && n_save_test > 0 && !kanode_internal_fk_train_ok(h, batch, true))
         return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
                                     "kanode_train_forward_tsit5: not supported (the test problem needs the one-workgroup "
@@ -2364,6 +2368,7 @@ static kanode_status train_tsit5_impl(bool forward, kanode_handle* h, void* p, v
     a.grad = (double*)grad;
     a.p_before = (double*)p_before;
     a.counts = counts;
+    a.act_reg = forward ? 0.0 : kanode_get_l1_penalty(h);
     int64_t res[2] = {0, 0};
     if (forward) SOLVE_TRY(kanode_internal_fk_train(h, batch, &a, meta, res, st));
     else SOLVE_TRY(kanode_internal_chain_train(h, &a, meta, res, st));

@@ -12,6 +12,7 @@ from .rhs import ChainRHS, FisherKPPRHS, fisher_kpp_laplacian, layer_apply, rhs_
 from .ode import Solution, Tsit5Options, solve
 from .adjoint import DenseRecord, interpolating_adjoint
 from .train import Adam, FusedAdam, Trainer, mse_loss, reg_loss
+from .sparse import prune, prune_nodes, prune_params
 from . import checkpoint, comm, tp
 from .tp import GridShardedChainRHS
 
@@ -20,5 +21,5 @@ __all__ = [
     "KanodeError", "LIB_PATH", "lib", "KanodeHandle", "LayerCfg", "Chain", "KDense", "glorot_uniform",
     "linrange_f32", "ChainRHS", "FisherKPPRHS", "fisher_kpp_laplacian", "layer_apply", "rhs_apply",
     "Solution", "Tsit5Options", "solve", "Adam", "FusedAdam", "Trainer", "mse_loss", "reg_loss", "checkpoint", "comm", "tp",
-    "GridShardedChainRHS",
+    "GridShardedChainRHS", "prune", "prune_nodes", "prune_params",
 ]

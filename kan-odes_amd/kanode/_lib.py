@@ -150,6 +150,9 @@ SIGNATURES = [
                                              C.c_int64, _P]),
     ("kanode_layer_vjp", C.c_int, [_H, C.c_int32, _P, _P, _P, _P, _P, C.c_int64, _P]),
     ("kanode_edge_activations", C.c_int, [_H, C.c_int32, _P, _P, _P, C.c_int64, _P]),
+    ("kanode_edge_scores", C.c_int, [_H, C.c_int32, _P, _P, _P, C.c_int64, _P]),
+    ("kanode_set_l1_penalty", C.c_int, [_H, C.c_double]),
+    ("kanode_get_l1_penalty", C.c_double, [_H]),
     ("kanode_adam_step", C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_double,
                                    C.c_double, C.c_double, C.c_double, C.c_double, _P]),
     ("kanode_train_supported", C.c_int32, [_H, C.c_int64]),

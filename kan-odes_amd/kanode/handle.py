@@ -397,16 +397,30 @@ class KanodeHandle:
         return self._train("kanode_train_forward_tsit5", p, m, v, u0, t0, tf, saveat, target, opts, eta, beta, eps,
                            beta_t, n_iters, test, record)
 
+    def set_l1_penalty(self, act_reg: float) -> None:
+        """kanode_set_l1_penalty: λ of train_tsit5's loss term λ·Σ|p| (finite, >= 0; 0 = plain MSE)."""
+        L.check(L.lib().kanode_set_l1_penalty(self._h, float(act_reg)), self._h, "kanode_set_l1_penalty")
+
+    def get_l1_penalty(self) -> float:
+        return float(L.lib().kanode_get_l1_penalty(self._h))
+
     def train_tsit5(self, p, m, v, u0, t0: float, tf: float, saveat, target, opts: "L.SolverOptsC", eta: float,
-                    beta, eps: float, beta_t, n_iters: int, test=None, record: bool = False):
+                    beta, eps: float, beta_t, n_iters: int, test=None, record: bool = False, l1: float = 0.0):
         """n_iters whole training iterations in one launch (kanode_train_tsit5): p, m, v are updated in place.
         test: None or (tf_test, saveat_test, target_test).  Returns a dict: loss (n_iters,), loss_test (n_iters,)
         or None, with record grad / p_before (n_iters, P) and counts (n_iters, 4), and iters_done, stop (a
         _lib.TRAIN_STOP name), error (the library's message when the loop stopped early, else None).  loss[it] is
         the loss at p_it, before the update; loss_test[it] at p_{it+1}.  An unsupported shape or a bad argument
-        raises KanodeError; a stopped loop does not (the caller reads iters_done)."""
-        return self._train("kanode_train_tsit5", p, m, v, u0, t0, tf, saveat, target, opts, eta, beta, eps, beta_t,
-                           n_iters, test, record)
+        raises KanodeError; a stopped loop does not (the caller reads iters_done).
+        l1: the weight λ of the sparsity term (loss + λ·Σ|p|, gradient + λ·sign(p)), set on the handle for this call
+        and restored afterwards (so the call's penalty is always `l1`, whatever set_l1_penalty left there)."""
+        old = self.get_l1_penalty()
+        self.set_l1_penalty(l1)
+        try:
+            return self._train("kanode_train_tsit5", p, m, v, u0, t0, tf, saveat, target, opts, eta, beta, eps,
+                               beta_t, n_iters, test, record)
+        finally:
+            self.set_l1_penalty(old)
 
     def _train(self, name, p, m, v, u0, t0, tf, saveat, target, opts, eta, beta, eps, beta_t, n_iters, test, record):
         """The call of train_tsit5 / train_forward_tsit5 (the two entries share their signature)."""
@@ -521,3 +535,16 @@ class KanodeHandle:
         L.check(L.lib().kanode_edge_activations(self._h, layer, _ptr(p_layer), _ptr(x), _ptr(act), K,
                                                 _stream(self.device)), self._h, "kanode_edge_activations")
         return act
+
+    def edge_scores(self, layer: int, p_layer: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """scores (I, O) with scores[i, o] = max_k |φ_{o,i}(x[k, i])| (kanode_edge_scores: what the reference's prune
+        reads from activation_getter, LV_driver_KANODE.jl:79-80), without the (K, I, O) array and for any out_dims.
+        A NaN activation makes its edge's score NaN."""
+        cfg = self.layers[layer]
+        K = x.shape[0]
+        self._check_t(p_layer, (cfg.param_length,), "p_layer")
+        self._check_t(x, (K, cfg.in_dims), "x")
+        scores = torch.empty((cfg.in_dims, cfg.out_dims), dtype=self.dtype, device=self.device)
+        L.check(L.lib().kanode_edge_scores(self._h, layer, _ptr(p_layer), _ptr(x), _ptr(scores), K,
+                                           _stream(self.device)), self._h, "kanode_edge_scores")
+        return scores

@@ -107,6 +107,12 @@ class KDense:
             p = torch.as_tensor(self.flatten(p), dtype=x.dtype, device=x.device)
         return self._handle(x.dtype, x.device).edge_activations(0, p.contiguous(), x.contiguous())
 
+    def edge_scores(self, x: torch.Tensor, p) -> torch.Tensor:
+        """scores (I, O) = max over the K samples of |edge_activations| (kanode_edge_scores), for any out_dims."""
+        if isinstance(p, dict):
+            p = torch.as_tensor(self.flatten(p), dtype=x.dtype, device=x.device)
+        return self._handle(x.dtype, x.device).edge_scores(0, p.contiguous(), x.contiguous())
+
 
 class Chain:
     """Lux.Chain of KDense layers; `setup` returns the flat ComponentArray vector."""
@@ -172,6 +178,23 @@ class Chain:
         if key not in self._handles:
             self._handles[key] = KanodeHandle(self.cfgs, dtype=dtype, rhs_kind="chain", device=device)
         return self._handles[key]
+
+    def edge_scores(self, x: torch.Tensor, p) -> list:
+        """[scores_l (I_l, O_l)] for every layer, x (K, I_0) propagated through the layers with the layer forward
+        (Activation_getter.jl:39: each layer is scored on the output of the one before)."""
+        if not isinstance(p, torch.Tensor):
+            p = torch.as_tensor(self.flatten(p) if isinstance(p, (list, tuple)) else np.asarray(p),
+                                dtype=x.dtype, device=x.device)
+        hd = self.handle(x.dtype, x.device)
+        if tuple(p.shape) != (hd.P,):
+            raise ValueError(f"p has shape {tuple(p.shape)}, expected ({hd.P},)")
+        out, h = [], x.reshape(-1, self.layers[0].in_dims).contiguous()
+        for l, off in enumerate(self.layer_offsets()):
+            pl = p.detach()[off:off + self.layers[l].parameterlength()].contiguous()
+            out.append(hd.edge_scores(l, pl, h))
+            if l + 1 < len(self.layers):
+                h = hd.layer_forward(l, pl, h)
+        return out
 
     def __call__(self, x: torch.Tensor, p, st):
         """Chain(x, p, st) -> (y, st), differentiable in x and p."""

@@ -167,12 +167,13 @@ class Trainer:
         return solve(self.rhs, self.u0, self.tspan, p, self.saveat, self.solver, sensealg=self.sensealg)
 
     def _fast_path(self):
-        """(saveat list, path) with path "forward" / "interpolating_adjoint" for the native plain-MSE step, or None."""
+        """(saveat list, path) with path "forward" / "interpolating_adjoint" for the native plain-MSE step, or None.
+        (sparse_reg does not exclude it: loss_and_grad adds the L1 term to the native loss and gradient.)"""
         sv = _saveat_list(self.tspan, self.saveat)
         tf = float(self.tspan[1])
         sv = [s for s in sv if s <= tf + 1e-12 * max(1.0, abs(tf))]     # as solve() filters them
         sa = self.sensealg
-        fast = (not self.tp and not self.sparse_reg and tuple(self.target.shape) == (len(sv),) + tuple(self.u0.shape)
+        fast = (not self.tp and tuple(self.target.shape) == (len(sv),) + tuple(self.u0.shape)
                 and native_ok(self.rhs, self.u0, self.tspan, self.p, sv, self.solver))
         if sa == "auto":
             sa = "forward" if fast and forward_ok(self.rhs, self.u0, self.p) else "interpolating_adjoint"
@@ -215,12 +216,12 @@ class Trainer:
             # ForwardDiffSensitivity: one native call carrying ∂u/∂p (adjoint.native_mse_gradient_forward)
             loss, g, sol = native_mse_gradient_forward(self.rhs, self.u0, self.tspan, self.p, sv, self.solver,
                                                        self.target, pre=pre)
-            return loss.detach(), g, sol
+            return self._with_l1(loss.detach(), g) + (sol,)
         if path == "interpolating_adjoint":
             # the plain-MSE step through the two native calls directly (adjoint.native_mse_gradient)
             loss, g, sol = native_mse_gradient(self.rhs, self.u0, self.tspan, self.p, sv, self.solver, self.target,
                                                pre=pre)
-            return loss.detach(), g, sol
+            return self._with_l1(loss.detach(), g) + (sol,)
         p = self.p.detach().requires_grad_(True)
         sol = self.predict(p)
         if self.tp:   # Σ over the grid shards of these partial sums = the global mean
@@ -231,6 +232,15 @@ class Trainer:
             loss = loss + reg_loss(p, self.sparse_reg, 0.0)
         (g,) = torch.autograd.grad(loss, p)
         return loss.detach(), g.detach(), sol
+
+    def _with_l1(self, loss, g):
+        """The native plain-MSE (loss, gradient) with the sparsity term of the driver's sparse_on = 1 added
+        (LV_driver_KANODE.jl:187-201): loss + reg_loss(p, λ, 0) and g + λ·sign(p), formed on p's device before any
+        all-reduce.  An entry of p that is exactly zero makes the loss NaN, as reg_loss is there."""
+        if not self.sparse_reg:
+            return loss, g
+        p = self.p.detach()
+        return loss + reg_loss(p, self.sparse_reg, 0.0), g + self.sparse_reg * torch.sign(p).reshape(g.shape)
 
     def step(self) -> float:
         return self._step()[0]
@@ -259,13 +269,14 @@ class Trainer:
         return lv, g_own, sol
 
     def _native_run_path(self, with_test: bool = False):
-        """The device-resident loop run() takes, or None: "device_adjoint" (kanode_train_tsit5: the plain-MSE
-        InterpolatingAdjoint) or "device_forward" (kanode_train_forward_tsit5: the plain-MSE forward-mode gradient
-        of a small Fisher-KPP field, with_test: with its logged-loss solve), where the handle covers the shape, the
+        """The device-resident loop run() takes, or None: "device_adjoint" (kanode_train_tsit5: the MSE, plus the L1
+        term with sparse_reg, on the InterpolatingAdjoint) or "device_forward" (kanode_train_forward_tsit5: the
+        plain-MSE forward-mode gradient of a small Fisher-KPP field, never with sparse_reg; with_test: with its
+        logged-loss solve), where the handle covers the shape, the
         gradient is this rank's alone and the optimiser is FusedAdam."""
         hd = getattr(self.rhs, "hd", None)
         if (hd is None or self.sensealg not in ("interpolating_adjoint", "forward", "auto") or self.group is not None
-                or self.tp or self.sparse_reg or type(self.opt) is not FusedAdam or not self.p.is_cuda):
+                or self.tp or type(self.opt) is not FusedAdam or not self.p.is_cuda):
             return None
         if self.p.dtype != torch.float64 or not (self.p.is_contiguous() and self.u0.is_contiguous()):
             return None
@@ -276,8 +287,8 @@ class Trainer:
         path = self._fast_path()[1]                       # ("auto" resolved; it turns fsens_wide on where it applies)
         if path == "interpolating_adjoint" and self.sensealg == "interpolating_adjoint" and hd.train_supported(B):
             return "device_adjoint"
-        if path == "forward" and hd.train_forward_supported(B, with_test):
-            return "device_forward"
+        if path == "forward" and not self.sparse_reg and hd.train_forward_supported(B, with_test):
+            return "device_forward"                       # (no L1 term in the Fisher-KPP loop: step() serves it)
         return None
 
     def run(self, n_iters: int, test=None, chunk: int = 256, record: bool = False) -> dict:
@@ -289,7 +300,8 @@ class Trainer:
         adjoint naccept, nreject).
 
         Where the handle covers it (one Lotka-Volterra trajectory on the InterpolatingAdjoint, or a small Fisher-KPP
-        field on the forward-mode gradient -- explicitly or through "auto" --; fp64, plain MSE, FusedAdam, no group)
+        field on the forward-mode gradient -- explicitly or through "auto" --; fp64, FusedAdam, no group; sparse_reg adds
+        the L1 term inside the Lotka-Volterra loop and sends a Fisher-KPP field to the host loop)
         the iterations run on the device (self.last_run says which loop ran: "device_adjoint", "device_forward" or
         "host"; on the forward loop there is no adjoint, and counts[:, 2:] are the logged-loss solve's naccept and nreject
         when a test problem is given, else zero), at most `chunk` per kernel launch (no single kernel runs for long on a shared
@@ -355,9 +367,9 @@ class Trainer:
         parts, left, err = [], n_iters, None
         while left > 0 and err is None:
             k = min(left, chunk)
-            call = hd.train_forward_tsit5 if forward else hd.train_tsit5
+            call, kw = (hd.train_forward_tsit5, {}) if forward else (hd.train_tsit5, {"l1": float(self.sparse_reg)})
             r = call(self.p, mt, vt, self.u0, float(self.tspan[0]), float(self.tspan[1]), sv, target, oc,
-                     self.opt.eta, (b1, b2), self.opt.eps, bp, k, test=test, record=record)
+                     self.opt.eta, (b1, b2), self.opt.eps, bp, k, test=test, record=record, **kw)
             d = r["iters_done"]
             for _ in range(d):                            # Flux's βp .*= β, once per iteration done
                 bp[0] *= b1
