@@ -18,6 +18,7 @@
 #include <string>
 #include <type_traits>
 
+#include "kan_buf.hpp"
 #include "kan_device.hpp"
 #include "kan_kernels.hpp"
 #include "kanode_internal.hpp"
@@ -42,22 +43,22 @@ struct kanode_handle {
     int n_layers = 0;
     LayerConst hlc[KANODE_MAX_LAYERS];
     LayerKind kind[KANODE_MAX_LAYERS];
-    LayerConst* dlc = nullptr;        // device copy
+    kan::DevBuf dlc_buf;              // device copy
+    LayerConst* dlc() const { return dlc_buf.as<LayerConst>(); }
     int64_t P = 0;
     int64_t n_in = 0, n_out = 0;      // state length (input / output of the RHS)
     size_t esize = 8;
     int max_layer_P = 0;
     int max_dim = 0;
     // workspaces (device)
-    void* slab = nullptr;
-    size_t slab_bytes = 0;
-    void* ws = nullptr;               // chain activations / gradients
-    size_t ws_bytes = 0;
+    kan::DevBuf slab;
+    kan::DevBuf ws;                   // chain activations / gradients
     int64_t reserved_batch = 0;
     // piecewise-polynomial pointwise RHS (kan_pp.hip)
     kan::PPConst hpc{};
-    kan::PPConst* dpc = nullptr;
-    double* dtable = nullptr;
+    kan::DevBuf dpc_buf, dtable_buf;
+    kan::PPConst* dpc() const { return dpc_buf.as<kan::PPConst>(); }
+    double* dtable() const { return dtable_buf.as<double>(); }
     bool pp_on = false;
     // evaluation-strategy options (kanode_set_option; read here, never from the environment per launch)
     bool fused_step = true;           // KANODE_OPT_FUSED_STEP
@@ -76,7 +77,7 @@ struct kanode_handle {
     double l1_penalty = 0.0;          // kanode_set_l1_penalty: λ of kanode_train_tsit5's loss term λ·Σ|p|
     std::vector<double> adj_steps;    // the last kanode_adjoint_tsit5's accepted step sizes (when recorded)
     bool adj_fused_finish = false;    // KANODE_OPT_ADJ_FUSED_FINISH (measured even with the finish launch)
-    unsigned* fin_ctr = nullptr;      // its two arrival counters (device, zeroed at allocation)
+    kan::DevBuf fin_ctr;              // its two arrival counters (unsigned, zeroed at allocation)
     // the surrogate pair's deferred adjoint stage: its second launch, held until the next stage is issued
     // (then both run as kd_vjp_pair_ba_kernel) or kanode_internal_vjp_flush; pair_par picks the buffers of
     // the ping-pong pairs (hidden / dot-product partials, basis store, y, λs) the next stage writes
@@ -94,26 +95,22 @@ struct kanode_handle {
     kanode_solution* solve_cache = nullptr;
     // the device-resident training loop (kanode_train_tsit5): result words | dense-output block | meta, and the
     // meta bytes last uploaded
-    void* train_buf = nullptr;
-    size_t train_bytes = 0;
+    kan::DevBuf train_buf;
     std::vector<char> train_meta;
     size_t train_meta_off = 0;        // where in train_buf those bytes lie
     // table reuse inside one integrator solve (p constant): build each table set once
     bool hold_tables = false;
     bool built_phi = false, built_vjp = false;
     // adjoint stages whose dp / error reductions wait for kanode_internal_vjp_flush (one launch)
-    void* defer_slab = nullptr;
-    void* cstep_slab = nullptr;       // the fused small-chain adjoint step's six stage regions (grown on demand)
-    size_t cstep_bytes = 0;
-    void* step_slab = nullptr;        // fused adjoint step: six stages' moment rows + error partials
+    kan::DevBuf defer_slab;
+    kan::DevBuf cstep_slab;           // the fused small-chain adjoint step's six stage regions (grown on demand)
+    kan::DevBuf step_slab;            // fused adjoint step: six stages' moment rows + error partials
     kan::FinishJobs jobs{};
     int njobs = 0;
     // stage input y for kanode_rhs_stage's unfused path
-    void* stage_ws = nullptr;
-    size_t stage_ws_bytes = 0;
+    kan::DevBuf stage_ws;
     // host staging (device buffers) for *_host calls
-    void* stage = nullptr;
-    size_t stage_bytes = 0;
+    kan::DevBuf stage;
     std::string err;
 };
 
@@ -332,26 +329,29 @@ size_t chain_ws_bytes(const kanode_handle* h, int64_t B) { return (size_t)ws_lay
 
 kanode_status flush_pair(kanode_handle* h, hipStream_t st);
 
-kanode_status ensure_ws(kanode_handle* h, int64_t B, hipStream_t st) {
-    const size_t need = h->spec.rhs_kind == KANODE_RHS_CHAIN ? chain_ws_bytes(h, B) : 0;
-    if (need <= h->ws_bytes) return KANODE_OK;
-    if (is_capturing(st))
-        return fail(h, KANODE_ERR_CAPTURE, "batch exceeds reserved workspace during stream capture; call kanode_reserve");
+// the workspace holds `need` bytes (contents not kept): never grown under capture, and only once what reads it has run
+kanode_status grow_ws(kanode_handle* h, size_t need, hipStream_t st, const char* capture_msg) {
+    if (need <= h->ws.bytes()) return KANODE_OK;
+    if (is_capturing(st)) return fail(h, KANODE_ERR_CAPTURE, capture_msg);
     // a deferred surrogate-pair stage reads the old workspace: launch it before the buffer goes away
     if (kanode_status s = flush_pair(h, st); s != KANODE_OK) return s;
     HIP_TRY(h, hipStreamSynchronize(st));
-    if (h->ws) HIP_TRY(h, hipFree(h->ws));
-    h->ws = nullptr;
-    h->ws_bytes = 0;
-    HIP_TRY(h, hipMalloc(&h->ws, need));
-    h->ws_bytes = need;
+    HIP_TRY(h, h->ws.reserve(need));
     return KANODE_OK;
+}
+kanode_status ensure_ws(kanode_handle* h, int64_t B, hipStream_t st) {
+    return grow_ws(h, h->spec.rhs_kind == KANODE_RHS_CHAIN ? chain_ws_bytes(h, B) : 0, st,
+                   "batch exceeds reserved workspace during stream capture; call kanode_reserve");
+}
+// ... and the Fisher-KPP VJP's λJ when the caller passes none
+kanode_status ensure_fk_ws(kanode_handle* h, int64_t B, hipStream_t st) {
+    return grow_ws(h, (size_t)(h->spec.nx * B) * h->esize, st, "workspace too small during capture");
 }
 
 // The wide kernels need the chain workspace's slab (sized by ensure_ws(K)).
 template <typename T>
 T* wide_slab(kanode_handle* h, int64_t K) {
-    return (T*)h->ws + ws_layout(h, K).wslab;
+    return (T*)h->ws.ptr() + ws_layout(h, K).wslab;
 }
 
 template <typename T>
@@ -359,13 +359,13 @@ kanode_status layer_fwd_t(kanode_handle* h, int l, const T* p_full, const T* x, 
     const LayerConst& hl = h->hlc[l];
     switch (h->kind[l]) {
     case KIND_COL:
-        HIP_TRY(h, kan::launch_kd_fwd_col<T>(hl, h->dlc + l, p_full, x, y, K, st));
+        HIP_TRY(h, kan::launch_kd_fwd_col<T>(hl, h->dlc() + l, p_full, x, y, K, st));
         return KANODE_OK;
     case KIND_WIDE_IN:
-        HIP_TRY(h, kan::launch_kd_fwd_widein<T>(hl, h->dlc + l, p_full, x, y, wide_slab<T>(h, K), K, st));
+        HIP_TRY(h, kan::launch_kd_fwd_widein<T>(hl, h->dlc() + l, p_full, x, y, wide_slab<T>(h, K), K, st));
         return KANODE_OK;
     case KIND_WIDE_OUT:
-        HIP_TRY(h, kan::launch_kd_fwd_wideout<T>(hl, h->dlc + l, p_full, x, y, K, st));
+        HIP_TRY(h, kan::launch_kd_fwd_wideout<T>(hl, h->dlc() + l, p_full, x, y, K, st));
         return KANODE_OK;
     }
     return fail(h, KANODE_ERR_UNSUPPORTED, "layer kind");
@@ -377,14 +377,14 @@ kanode_status layer_vjp_t(kanode_handle* h, int l, const T* p_full, const T* x, 
     const LayerConst& hl = h->hlc[l];
     switch (h->kind[l]) {
     case KIND_COL:
-        HIP_TRY(h, kan::launch_kd_vjp_col<T>(hl, h->dlc + l, p_full, x, yb, xb, pbar_full, (T*)h->slab, kSlabBlocks,
+        HIP_TRY(h, kan::launch_kd_vjp_col<T>(hl, h->dlc() + l, p_full, x, yb, xb, pbar_full, (T*)h->slab.ptr(), kSlabBlocks,
                                              K, st));
         return KANODE_OK;
     case KIND_WIDE_IN:
-        HIP_TRY(h, kan::launch_kd_vjp_widein<T>(hl, h->dlc + l, p_full, x, yb, xb, pbar_full, K, st));
+        HIP_TRY(h, kan::launch_kd_vjp_widein<T>(hl, h->dlc() + l, p_full, x, yb, xb, pbar_full, K, st));
         return KANODE_OK;
     case KIND_WIDE_OUT:
-        HIP_TRY(h, kan::launch_kd_vjp_wideout<T>(hl, h->dlc + l, p_full, x, yb, xb, pbar_full, wide_slab<T>(h, K), K,
+        HIP_TRY(h, kan::launch_kd_vjp_wideout<T>(hl, h->dlc() + l, p_full, x, yb, xb, pbar_full, wide_slab<T>(h, K), K,
                                                  st));
         return KANODE_OK;
     }
@@ -398,29 +398,29 @@ kanode_status rhs_t(kanode_handle* h, const T* p, const T* u, T* du, int64_t B, 
         const T cd = (T)(h->spec.diffusion * (-2.0 / dx2)), co = (T)(h->spec.diffusion * (1.0 / dx2));
         if constexpr (std::is_same<T, double>::value) {
             if (h->pp_on) {
-                HIP_TRY(h, kan::launch_fk_rhs_pp(h->hpc, h->hlc[0], h->dlc, h->dpc, p, h->dtable, cd, co, (int)h->spec.nx, u, du,
+                HIP_TRY(h, kan::launch_fk_rhs_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co, (int)h->spec.nx, u, du,
                                                  B, st, table_build(h, h->built_phi), h->grid_ovr.rhs));
                 return KANODE_OK;
             }
         }
-        HIP_TRY(h, kan::launch_fk_rhs<T>(h->hlc[0], h->dlc, p, cd, co, (int)h->spec.nx, u, du, B, st));
+        HIP_TRY(h, kan::launch_fk_rhs<T>(h->hlc[0], h->dlc(), p, cd, co, (int)h->spec.nx, u, du, B, st));
         return KANODE_OK;
     }
     bool all_col = h->n_layers > 1;
     for (int l = 0; l < h->n_layers; ++l) all_col = all_col && h->kind[l] == KIND_COL;
     if (all_col) {
-        const hipError_t e = kan::launch_kd_chain_col<T>(h->hlc, h->n_layers, h->dlc, p, h->P, u, du, B, st);
+        const hipError_t e = kan::launch_kd_chain_col<T>(h->hlc, h->n_layers, h->dlc(), p, h->P, u, du, B, st);
         if (e == hipSuccess) return KANODE_OK;
         if (e != hipErrorNotSupported) return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_col: ") + hipGetErrorString(e));
     }
     kanode_status s = ensure_ws(h, B, st);
     if (s != KANODE_OK) return s;
-    T* ws = (T*)h->ws;
+    T* ws = (T*)h->ws.ptr();
     const WsLayout wl = ws_layout(h, B);
     if (surrogate_pair(h)) {   // two launches: wide-in partials -> wide-out summing them itself
         T* ps = ws + wl.pslab;
-        HIP_TRY(h, kan::launch_kd_fwd_widein<T>(h->hlc[0], h->dlc, p, u, (T*)nullptr, ps, B, st));
-        HIP_TRY(h, kan::launch_kd_fwd_wideout<T>(h->hlc[1], h->dlc + 1, p, (const T*)nullptr, du, B, st, ps,
+        HIP_TRY(h, kan::launch_kd_fwd_widein<T>(h->hlc[0], h->dlc(), p, u, (T*)nullptr, ps, B, st));
+        HIP_TRY(h, kan::launch_kd_fwd_wideout<T>(h->hlc[1], h->dlc() + 1, p, (const T*)nullptr, du, B, st, ps,
                                                   kan::widein_chunks(h->hlc[0])));
         return KANODE_OK;
     }
@@ -443,26 +443,18 @@ kanode_status vjp_t(kanode_handle* h, const T* p, const T* u, const T* lam, T* l
         // lam_J is needed for the kernel's store; use workspace when the caller passes NULL
         T* out = lamJ;
         if (!out) {
-            kanode_status s = ensure_ws(h, B, st);
-            if (s != KANODE_OK) return s;
-            if (h->ws_bytes < (size_t)(h->spec.nx * B) * h->esize) {
-                if (is_capturing(st)) return fail(h, KANODE_ERR_CAPTURE, "workspace too small during capture");
-                HIP_TRY(h, hipStreamSynchronize(st));
-                if (h->ws) HIP_TRY(h, hipFree(h->ws));
-                HIP_TRY(h, hipMalloc(&h->ws, (size_t)(h->spec.nx * B) * h->esize));
-                h->ws_bytes = (size_t)(h->spec.nx * B) * h->esize;
-            }
-            out = (T*)h->ws;
+            if (kanode_status s = ensure_fk_ws(h, B, st); s != KANODE_OK) return s;
+            out = (T*)h->ws.ptr();
         }
         if constexpr (std::is_same<T, double>::value) {
             if (h->pp_on && kan::fk_vjp_pp_supported(h->hlc[0], (int)h->spec.nx)) {
-                HIP_TRY(h, kan::launch_fk_vjp_pp(h->hpc, h->hlc[0], h->dlc, h->dpc, p, h->dtable, cd, co,
-                                                 (int)h->spec.nx, u, lam, out, dp, (double*)h->slab, kSlabBlocks, B,
+                HIP_TRY(h, kan::launch_fk_vjp_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co,
+                                                 (int)h->spec.nx, u, lam, out, dp, (double*)h->slab.ptr(), kSlabBlocks, B,
                                                  st, table_build(h, h->built_vjp), h->grid_ovr.vjp));
                 return KANODE_OK;
             }
         }
-        HIP_TRY(h, kan::launch_fk_vjp<T>(h->hlc[0], h->dlc, p, cd, co, (int)h->spec.nx, u, lam, out, dp, (T*)h->slab,
+        HIP_TRY(h, kan::launch_fk_vjp<T>(h->hlc[0], h->dlc(), p, cd, co, (int)h->spec.nx, u, lam, out, dp, (T*)h->slab.ptr(),
                                          kSlabBlocks, B, st));
         return KANODE_OK;
     }
@@ -471,9 +463,9 @@ kanode_status vjp_t(kanode_handle* h, const T* p, const T* u, const T* lam, T* l
         for (int l = 0; l < h->n_layers; ++l) all_col = all_col && h->kind[l] == KIND_COL;
         if (all_col) {
             const kan::StageArgs<T> none{};
-            const hipError_t e = kan::launch_kd_chain_vjp_stage<T>(h->hlc, h->n_layers, h->dlc, p, h->P, u, none, lam,
-                                                                   none, nullptr, lamJ, dp, false, nullptr, h->slab,
-                                                                   h->slab_bytes, B, st);
+            const hipError_t e = kan::launch_kd_chain_vjp_stage<T>(h->hlc, h->n_layers, h->dlc(), p, h->P, u, none, lam,
+                                                                   none, nullptr, lamJ, dp, false, nullptr, h->slab.ptr(),
+                                                                   h->slab.bytes(), B, st);
             if (e == hipSuccess) return KANODE_OK;
             if (e != hipErrorNotSupported)
                 return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_vjp_stage: ") + hipGetErrorString(e));
@@ -481,7 +473,7 @@ kanode_status vjp_t(kanode_handle* h, const T* p, const T* u, const T* lam, T* l
     }
     kanode_status s = ensure_ws(h, B, st);
     if (s != KANODE_OK) return s;
-    T* ws = (T*)h->ws;
+    T* ws = (T*)h->ws.ptr();
     const WsLayout wl = ws_layout(h, B);
     if (surrogate_pair(h)) {
         T* ps = ws + wl.pslab;
@@ -491,7 +483,7 @@ kanode_status vjp_t(kanode_handle* h, const T* p, const T* u, const T* lam, T* l
             // two launches (launch_kd_vjp_pair): the wide-in forward blocks also form the wide-out dot
             // products' chunk partials; the wide-out parameter cotangents beside the wide-in pullback
             // (x̄ of the hidden layer formed per block)
-            const hipError_t e = kan::launch_kd_vjp_pair<T>(h->hlc[0], h->hlc[1], h->dlc, p, u, nullptr, lam, u, ps,
+            const hipError_t e = kan::launch_kd_vjp_pair<T>(h->hlc[0], h->hlc[1], h->dlc(), p, u, nullptr, lam, u, ps,
                                                             ws + wl.sslab, lamJ, dp, B, st, false, nullptr, 0,
                                                             nullptr, ws + wl.bslab);
             if (e == hipSuccess) return KANODE_OK;
@@ -500,10 +492,10 @@ kanode_status vjp_t(kanode_handle* h, const T* p, const T* u, const T* lam, T* l
         }
         // four launches: wide-in partials; the wide-out pullback's dot products and parameter
         // cotangents in one launch; its input cotangent; the wide-in pullback
-        HIP_TRY(h, kan::launch_kd_fwd_widein<T>(h->hlc[0], h->dlc, p, u, (T*)nullptr, ps, B, st));
-        HIP_TRY(h, kan::launch_kd_vjp_wideout<T>(h->hlc[1], h->dlc + 1, p, (const T*)nullptr, lam, hbar, dp,
+        HIP_TRY(h, kan::launch_kd_fwd_widein<T>(h->hlc[0], h->dlc(), p, u, (T*)nullptr, ps, B, st));
+        HIP_TRY(h, kan::launch_kd_vjp_wideout<T>(h->hlc[1], h->dlc() + 1, p, (const T*)nullptr, lam, hbar, dp,
                                                   ws + wl.wslab, B, st, ps, nb));
-        if (lamJ || dp) HIP_TRY(h, kan::launch_kd_vjp_widein<T>(h->hlc[0], h->dlc, p, u, hbar, lamJ, dp, B, st));
+        if (lamJ || dp) HIP_TRY(h, kan::launch_kd_vjp_widein<T>(h->hlc[0], h->dlc(), p, u, hbar, lamJ, dp, B, st));
         return KANODE_OK;
     }
     // forward recompute, keeping every hidden layer's input
@@ -557,8 +549,8 @@ kanode_status stage_t(kanode_handle* h, const T* p, const T* u, const kanode_sta
             kan::fk_stage_pp_supported(h->hpc, (int)h->spec.nx)) {
             const double dx2 = h->spec.dx * h->spec.dx;
             const double cd = h->spec.diffusion * (-2.0 / dx2), co = h->spec.diffusion * (1.0 / dx2);
-            HIP_TRY(h, kan::launch_fk_stage_pp(h->hpc, h->hlc[0], h->dlc, h->dpc, p, h->dtable, cd, co,
-                                               (int)h->spec.nx, u, sa, (double*)sg->y_out, (double*)h->slab,
+            HIP_TRY(h, kan::launch_fk_stage_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co,
+                                               (int)h->spec.nx, u, sa, (double*)sg->y_out, (double*)h->slab.ptr(),
                                                kSlabBlocks, err_out, du, B, st, table_build(h, h->built_phi),
                                                h->grid_ovr.rhs));
             return KANODE_OK;
@@ -569,8 +561,8 @@ kanode_status stage_t(kanode_handle* h, const T* p, const T* u, const kanode_sta
         bool all_col = true;
         for (int l = 0; l < h->n_layers; ++l) all_col = all_col && h->kind[l] == KIND_COL;
         if (all_col) {
-            const hipError_t e = kan::launch_kd_chain_col<T>(h->hlc, h->n_layers, h->dlc, p, h->P, u, du, B, st, &sa,
-                                                             (T*)sg->y_out, (double*)h->slab, kSlabBlocks, err_out);
+            const hipError_t e = kan::launch_kd_chain_col<T>(h->hlc, h->n_layers, h->dlc(), p, h->P, u, du, B, st, &sa,
+                                                             (T*)sg->y_out, (double*)h->slab.ptr(), kSlabBlocks, err_out);
             if (e == hipSuccess) return KANODE_OK;
             if (e != hipErrorNotSupported)
                 return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_col: ") + hipGetErrorString(e));
@@ -584,16 +576,16 @@ kanode_status stage_t(kanode_handle* h, const T* p, const T* u, const kanode_sta
         T* y = (T*)sg->y_out;
         if (!y && err_out) {
             if ((s = ensure_stage_ws(h, (size_t)n * sizeof(T), st)) != KANODE_OK) return s;
-            y = (T*)h->stage_ws;
+            y = (T*)h->stage_ws.ptr();
         }
-        T* ps = (T*)h->ws + ws_layout(h, B).pslab;
+        T* ps = (T*)h->ws.ptr() + ws_layout(h, B).pslab;
         kan::WideStageIn<T> si{};
         si.su = sa;
         si.y_out = y;
-        HIP_TRY(h, kan::launch_kd_fwd_widein<T>(h->hlc[0], h->dlc, p, u, (T*)nullptr, ps, B, st, &si));
-        HIP_TRY(h, kan::launch_kd_fwd_wideout<T>(h->hlc[1], h->dlc + 1, p, (const T*)nullptr, du, B, st, ps,
+        HIP_TRY(h, kan::launch_kd_fwd_widein<T>(h->hlc[0], h->dlc(), p, u, (T*)nullptr, ps, B, st, &si));
+        HIP_TRY(h, kan::launch_kd_fwd_wideout<T>(h->hlc[1], h->dlc() + 1, p, (const T*)nullptr, du, B, st, ps,
                                                   kan::widein_chunks(h->hlc[0])));
-        if (err_out) HIP_TRY(h, kan::launch_stage_error<T>(u, y, du, sa, (double*)h->slab, kSlabBlocks, err_out, n, st));
+        if (err_out) HIP_TRY(h, kan::launch_stage_error<T>(u, y, du, sa, (double*)h->slab.ptr(), kSlabBlocks, err_out, n, st));
         return KANODE_OK;
     }
     // unfused: y materialised (into y_out or the handle's stage workspace), RHS, error pass
@@ -601,26 +593,22 @@ kanode_status stage_t(kanode_handle* h, const T* p, const T* u, const kanode_sta
     if (!y) {
         kanode_status s = ensure_stage_ws(h, (size_t)n * sizeof(T), st);
         if (s != KANODE_OK) return s;
-        y = (T*)h->stage_ws;
+        y = (T*)h->stage_ws.ptr();
     }
     HIP_TRY(h, kan::launch_stage_lincomb<T>(u, sa, y, n, st));
     kanode_status s = rhs_t<T>(h, p, y, du, B, st);
     if (s != KANODE_OK) return s;
-    if (err_out) HIP_TRY(h, kan::launch_stage_error<T>(u, y, du, sa, (double*)h->slab, kSlabBlocks, err_out, n, st));
+    if (err_out) HIP_TRY(h, kan::launch_stage_error<T>(u, y, du, sa, (double*)h->slab.ptr(), kSlabBlocks, err_out, n, st));
     return KANODE_OK;
 }
 
 // stage workspace of at least `need` bytes (the unfused stage paths)
 kanode_status ensure_stage_ws(kanode_handle* h, size_t need, hipStream_t st) {
-    if (need <= h->stage_ws_bytes) return KANODE_OK;
+    if (need <= h->stage_ws.bytes()) return KANODE_OK;
     if (is_capturing(st)) return fail(h, KANODE_ERR_CAPTURE, "stage workspace too small during capture");
     if (kanode_status s = flush_pair(h, st); s != KANODE_OK) return s;   // (reads the old stage workspace)
     HIP_TRY(h, hipStreamSynchronize(st));
-    if (h->stage_ws) HIP_TRY(h, hipFree(h->stage_ws));
-    h->stage_ws = nullptr;
-    h->stage_ws_bytes = 0;
-    HIP_TRY(h, hipMalloc(&h->stage_ws, need));
-    h->stage_ws_bytes = need;
+    HIP_TRY(h, h->stage_ws.reserve(need));
     return KANODE_OK;
 }
 
@@ -648,22 +636,18 @@ constexpr size_t kDeferRegion = (size_t)(kSlabBlocks / 2) * (kan::kMaxGrid + 2);
 // one-launch adjoint step).  kanode_create allocates them for handles that can take that path; this
 // covers a handle whose table path was switched on later, and refuses to allocate under capture.
 kanode_status ensure_adjoint_slabs(kanode_handle* h, hipStream_t st, bool at_create = false) {
-    if (h->defer_slab && h->step_slab && h->fin_ctr) return KANODE_OK;
+    if (h->defer_slab.ptr() && h->step_slab.ptr() && h->fin_ctr.ptr()) return KANODE_OK;
     if (!at_create && is_capturing(st))
         return fail(h, KANODE_ERR_CAPTURE, "adjoint reduction slabs would be allocated during capture");
     const size_t defer = kDeferRegion * sizeof(double) * kan::kMaxFinishJobs;
     const size_t step = (size_t)(kSlabBlocks / 2) * (6 * (kan::kMaxGrid + 1) + 1) * sizeof(double);
-    if ((!h->defer_slab && hipMalloc(&h->defer_slab, defer) != hipSuccess) ||
-        (!h->step_slab && hipMalloc(&h->step_slab, step) != hipSuccess)) {
-        (void)hipGetLastError();
+    if (h->defer_slab.reserve(defer) != hipSuccess || h->step_slab.reserve(step) != hipSuccess)
         return fail(h, KANODE_ERR_ALLOC, "adjoint reduction slabs");
-    }
-    if (!h->fin_ctr) {   // the fused finish's arrival counters: zero here, and back to zero after every step
-        if (hipMalloc(&h->fin_ctr, 2 * sizeof(unsigned)) != hipSuccess ||
-            hipMemset(h->fin_ctr, 0, 2 * sizeof(unsigned)) != hipSuccess) {
+    if (!h->fin_ctr.ptr()) {   // the fused finish's arrival counters: zero here, and back to zero after every step
+        if (h->fin_ctr.reserve(2 * sizeof(unsigned)) != hipSuccess ||
+            hipMemset(h->fin_ctr.ptr(), 0, 2 * sizeof(unsigned)) != hipSuccess) {
             (void)hipGetLastError();
-            if (h->fin_ctr) (void)hipFree(h->fin_ctr);
-            h->fin_ctr = nullptr;
+            h->fin_ctr.reset();
             return fail(h, KANODE_ERR_ALLOC, "adjoint finish counters");
         }
     }
@@ -720,9 +704,9 @@ kanode_status vjp_stage_t(kanode_handle* h, const T* p, const T* u, const kanode
             if (defer && (dp || err_out)) {
                 if (h->njobs == kan::kMaxFinishJobs && (s = vjp_flush(h, st)) != KANODE_OK) return s;
                 if ((s = ensure_adjoint_slabs(h, st)) != KANODE_OK) return s;
-                double* region = (double*)h->defer_slab + (size_t)h->njobs * kDeferRegion;
+                double* region = (double*)h->defer_slab.ptr() + (size_t)h->njobs * kDeferRegion;
                 int grid = 0;
-                HIP_TRY(h, kan::launch_fk_vjp_stage_pp(h->hpc, h->hlc[0], h->dlc, h->dpc, p, h->dtable, cd, co,
+                HIP_TRY(h, kan::launch_fk_vjp_stage_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co,
                                                        (int)h->spec.nx, u, su, lam, sl, (double*)adj->y_out, lamJ,
                                                        dp, dp_assign, err_out, region, kSlabBlocks, B, st,
                                                        table_build(h, h->built_vjp), &grid, h->grid_ovr.vjp));
@@ -735,9 +719,9 @@ kanode_status vjp_stage_t(kanode_handle* h, const T* p, const T* u, const kanode
                 jb.assign = dp_assign ? 1 : 0;
                 return KANODE_OK;
             }
-            HIP_TRY(h, kan::launch_fk_vjp_stage_pp(h->hpc, h->hlc[0], h->dlc, h->dpc, p, h->dtable, cd, co,
+            HIP_TRY(h, kan::launch_fk_vjp_stage_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co,
                                                    (int)h->spec.nx, u, su, lam, sl, (double*)adj->y_out, lamJ, dp,
-                                                   dp_assign, err_out, (double*)h->slab, kSlabBlocks, B, st,
+                                                   dp_assign, err_out, (double*)h->slab.ptr(), kSlabBlocks, B, st,
                                                    table_build(h, h->built_vjp), nullptr, h->grid_ovr.vjp));
             return KANODE_OK;
         }
@@ -748,8 +732,8 @@ kanode_status vjp_stage_t(kanode_handle* h, const T* p, const T* u, const kanode
         for (int l = 0; l < h->n_layers; ++l) all_col = all_col && h->kind[l] == KIND_COL;
         if (all_col) {
             const hipError_t e = kan::launch_kd_chain_vjp_stage<T>(
-                h->hlc, h->n_layers, h->dlc, p, h->P, u, su, lam, sl, (T*)adj->y_out, lamJ, dp, dp_assign,
-                adj->want_error ? (double*)adj->error_sumsq : nullptr, h->slab, h->slab_bytes, B, st);
+                h->hlc, h->n_layers, h->dlc(), p, h->P, u, su, lam, sl, (T*)adj->y_out, lamJ, dp, dp_assign,
+                adj->want_error ? (double*)adj->error_sumsq : nullptr, h->slab.ptr(), h->slab.bytes(), B, st);
             if (e == hipSuccess) return KANODE_OK;
             if (e != hipErrorNotSupported)
                 return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_vjp_stage: ") + hipGetErrorString(e));
@@ -761,15 +745,15 @@ kanode_status vjp_stage_t(kanode_handle* h, const T* p, const T* u, const kanode
         // Deferred stages (the integrator's, `defer`) run lazily: a stage's second launch waits for the next
         // stage and both run as one (launch_pair_second with next), alternating the ping-pong buffers.
         const bool lazy = defer && h->pair_vjp && h->pair_fuse;
-        if (!lazy || chain_ws_bytes(h, B) > h->ws_bytes || 4 * (size_t)n * sizeof(T) > h->stage_ws_bytes)
+        if (!lazy || chain_ws_bytes(h, B) > h->ws.bytes() || 4 * (size_t)n * sizeof(T) > h->stage_ws.bytes())
             if ((s = flush_pair(h, st)) != KANODE_OK) return s;   // (and before any buffer is reallocated)
         if ((s = ensure_ws(h, B, st)) != KANODE_OK) return s;
         if ((s = ensure_stage_ws(h, 4 * (size_t)n * sizeof(T), st)) != KANODE_OK) return s;
         const int par = lazy ? h->pair_par : 0;
         const WsLayout wl = ws_layout(h, B);
-        T* ws = (T*)h->ws;
+        T* ws = (T*)h->ws.ptr();
         const int64_t pp = par ? wl.pair2 - wl.pslab : 0;   // the ping-pong pairs' second buffer
-        T* y = (T*)h->stage_ws + (size_t)par * 2 * n;
+        T* y = (T*)h->stage_ws.ptr() + (size_t)par * 2 * n;
         T* ls = adj->y_out ? (T*)adj->y_out : y + n;
         T* ps = ws + wl.pslab + pp;
         T* hbar = ws + wl.g0;
@@ -786,8 +770,8 @@ kanode_status vjp_stage_t(kanode_handle* h, const T* p, const T* u, const kanode
             double* err_out = adj->want_error ? (double*)adj->error_sumsq : nullptr;
             kan::PairPlan<T> pl;
             const bool host_parts = err_out && h->err_parts && h->err_nparts;
-            e = kan::plan_kd_vjp_pair<T>(h->hlc[0], h->hlc[1], h->dlc, p, u, &si, lam, y, ps, ws + wl.sslab + pp, lamJ,
-                                         dp, B, dp_assign, host_parts ? h->err_parts : (double*)h->slab, kSlabBlocks,
+            e = kan::plan_kd_vjp_pair<T>(h->hlc[0], h->hlc[1], h->dlc(), p, u, &si, lam, y, ps, ws + wl.sslab + pp, lamJ,
+                                         dp, B, dp_assign, host_parts ? h->err_parts : (double*)h->slab.ptr(), kSlabBlocks,
                                          err_out, ws + wl.bslab + pp, &pl);
             if (e == hipSuccess) {
                 if (host_parts && pl.err_out) {   // the host sums the partials: no final launch
@@ -811,8 +795,8 @@ kanode_status vjp_stage_t(kanode_handle* h, const T* p, const T* u, const kanode
             double* err_out = adj->want_error ? (double*)adj->error_sumsq : nullptr;
             const bool host_parts = err_out && h->err_parts && h->err_nparts;   // (as the lazy path)
             kan::PairPlan<T> pl;
-            e = kan::plan_kd_vjp_pair<T>(h->hlc[0], h->hlc[1], h->dlc, p, u, &si, lam, y, ps, ws + wl.sslab + pp, lamJ,
-                                         dp, B, dp_assign, host_parts ? h->err_parts : (double*)h->slab, kSlabBlocks,
+            e = kan::plan_kd_vjp_pair<T>(h->hlc[0], h->hlc[1], h->dlc(), p, u, &si, lam, y, ps, ws + wl.sslab + pp, lamJ,
+                                         dp, B, dp_assign, host_parts ? h->err_parts : (double*)h->slab.ptr(), kSlabBlocks,
                                          err_out, ws + wl.bslab + pp, &pl);
             if (e == hipSuccess) {
                 if (host_parts && pl.err_out) {
@@ -827,25 +811,25 @@ kanode_status vjp_stage_t(kanode_handle* h, const T* p, const T* u, const kanode
             err_done = e == hipSuccess && err_out != nullptr;
         }
         if (e != hipSuccess) {
-            HIP_TRY(h, kan::launch_kd_fwd_widein<T>(h->hlc[0], h->dlc, p, u, (T*)nullptr, ps, B, st, &si));
-            HIP_TRY(h, kan::launch_kd_vjp_wideout<T>(h->hlc[1], h->dlc + 1, p, (const T*)nullptr, ls, hbar, dp,
+            HIP_TRY(h, kan::launch_kd_fwd_widein<T>(h->hlc[0], h->dlc(), p, u, (T*)nullptr, ps, B, st, &si));
+            HIP_TRY(h, kan::launch_kd_vjp_wideout<T>(h->hlc[1], h->dlc() + 1, p, (const T*)nullptr, ls, hbar, dp,
                                                       ws + wl.wslab, B, st, ps, nb, dp_assign));
-            HIP_TRY(h, kan::launch_kd_vjp_widein<T>(h->hlc[0], h->dlc, p, y, hbar, lamJ, dp, B, st, dp_assign));
+            HIP_TRY(h, kan::launch_kd_vjp_widein<T>(h->hlc[0], h->dlc(), p, y, hbar, lamJ, dp, B, st, dp_assign));
         }
         if (adj->want_error && !err_done)
-            HIP_TRY(h, kan::launch_stage_error<T>(lam, ls, lamJ, sl, (double*)h->slab, kSlabBlocks,
+            HIP_TRY(h, kan::launch_stage_error<T>(lam, ls, lamJ, sl, (double*)h->slab.ptr(), kSlabBlocks,
                                                   (double*)adj->error_sumsq, n, st));
         return KANODE_OK;
     }
     if (dp && dp_assign) HIP_TRY(h, hipMemsetAsync(dp, 0, (size_t)h->P * sizeof(T), st));
     if ((s = ensure_stage_ws(h, 2 * (size_t)n * sizeof(T), st)) != KANODE_OK) return s;
-    T* y = su.nk ? (T*)h->stage_ws : (T*)u;
-    T* ls = adj->y_out ? (T*)adj->y_out : (sl.nk ? (T*)h->stage_ws + n : (T*)lam);
+    T* y = su.nk ? (T*)h->stage_ws.ptr() : (T*)u;
+    T* ls = adj->y_out ? (T*)adj->y_out : (sl.nk ? (T*)h->stage_ws.ptr() + n : (T*)lam);
     if (su.nk) HIP_TRY(h, kan::launch_stage_lincomb<T>(u, su, y, n, st));
     if (sl.nk || adj->y_out) HIP_TRY(h, kan::launch_stage_lincomb<T>(lam, sl, ls, n, st));
     if ((s = vjp_t<T>(h, p, y, ls, lamJ, dp, B, st)) != KANODE_OK) return s;
     if (adj->want_error)
-        HIP_TRY(h, kan::launch_stage_error<T>(lam, ls, lamJ, sl, (double*)h->slab, kSlabBlocks,
+        HIP_TRY(h, kan::launch_stage_error<T>(lam, ls, lamJ, sl, (double*)h->slab.ptr(), kSlabBlocks,
                                               (double*)adj->error_sumsq, n, st));
     return KANODE_OK;
 }
@@ -879,13 +863,13 @@ kanode_status layer_fwd_stage_t(kanode_handle* h, int l, const T* p_full, const 
         si.lam = lam;
         si.sl = sla;
         si.ls_out = lam ? (T*)sl->y_out : nullptr;
-        HIP_TRY(h, kan::launch_kd_fwd_widein<T>(hl, h->dlc + l, p_full, x, out, wide_slab<T>(h, K), K, st, &si));
+        HIP_TRY(h, kan::launch_kd_fwd_widein<T>(hl, h->dlc() + l, p_full, x, out, wide_slab<T>(h, K), K, st, &si));
         return KANODE_OK;
     }
     T* y = (T*)sx->y_out;
     if (!y) {
         if ((s = ensure_stage_ws(h, (size_t)n * sizeof(T), st)) != KANODE_OK) return s;
-        y = (T*)h->stage_ws;
+        y = (T*)h->stage_ws.ptr();
     }
     HIP_TRY(h, kan::launch_stage_lincomb<T>(x, su, y, n, st));
     if (lam) HIP_TRY(h, kan::launch_stage_lincomb<T>(lam, sla, (T*)sl->y_out, n, st));
@@ -969,17 +953,17 @@ kanode_status kanode_create(const kanode_spec* spec, kanode_handle** out) {
     }
     hipError_t e = hipSetDevice(spec->device);
     if (e != hipSuccess) return bail(fail(h, KANODE_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(e)));
-    if ((e = hipMalloc(&h->dlc, sizeof(LayerConst) * h->n_layers)) != hipSuccess)
+    if ((e = h->dlc_buf.reserve(sizeof(LayerConst) * h->n_layers)) != hipSuccess)
         return bail(fail(h, KANODE_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)));
-    if ((e = hipMemcpy(h->dlc, h->hlc, sizeof(LayerConst) * h->n_layers, hipMemcpyHostToDevice)) != hipSuccess)
+    if ((e = hipMemcpy(h->dlc(), h->hlc, sizeof(LayerConst) * h->n_layers, hipMemcpyHostToDevice)) != hipSuccess)
         return bail(fail(h, KANODE_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e)));
     if (spec->rhs_kind == KANODE_RHS_POINTWISE_PERIODIC_LAPLACIAN) {
         make_pp_const(h->hlc[0], spec->dtype, spec->nx, h->hpc);
         if (h->hpc.enabled) {
-            if ((e = hipMalloc(&h->dpc, sizeof(kan::PPConst))) != hipSuccess ||
-                (e = hipMemcpy(h->dpc, &h->hpc, sizeof(kan::PPConst), hipMemcpyHostToDevice)) != hipSuccess ||
-                (e = hipMalloc(&h->dtable, sizeof(double) * kan::pp_tables_doubles(h->hpc.ni))) != hipSuccess ||
-                (e = hipMemset(h->dtable, 0, sizeof(double) * kan::pp_tables_doubles(h->hpc.ni))) != hipSuccess)
+            if ((e = h->dpc_buf.reserve(sizeof(kan::PPConst))) != hipSuccess ||
+                (e = hipMemcpy(h->dpc(), &h->hpc, sizeof(kan::PPConst), hipMemcpyHostToDevice)) != hipSuccess ||
+                (e = h->dtable_buf.reserve(sizeof(double) * kan::pp_tables_doubles(h->hpc.ni))) != hipSuccess ||
+                (e = hipMemset(h->dtable(), 0, sizeof(double) * kan::pp_tables_doubles(h->hpc.ni))) != hipSuccess)
                 return bail(fail(h, KANODE_ERR_HIP, std::string("pp table: ") + hipGetErrorString(e)));
             h->pp_on = true;
             if (kan::fk_vjp_pp_supported(h->hlc[0], (int)spec->nx)) {
@@ -991,18 +975,15 @@ kanode_status kanode_create(const kanode_spec* spec, kanode_handle** out) {
     // per-block partial rows: the column-kernel VJPs need a layer's (an all-column chain's) P per row;
     // the wide kernels keep their partials in the chain workspace; stage / error / table-VJP rows
     // need at most kMaxGrid + 2 doubles
-    {
-        bool all_col = true;
-        int64_t col_P = 0;
-        for (int l = 0; l < h->n_layers; ++l) {
-            if (h->kind[l] == KIND_COL) col_P = std::max<int64_t>(col_P, layer_P(h->hlc[l]));
-            else all_col = false;
-        }
-        if (all_col) col_P = std::max<int64_t>(col_P, h->P);
-        const size_t row = std::max<size_t>((size_t)col_P * h->esize, (size_t)(kan::kMaxGrid + 2) * sizeof(double));
-        h->slab_bytes = (size_t)kSlabBlocks * row;
+    bool all_col = true;
+    int64_t col_P = 0;
+    for (int l = 0; l < h->n_layers; ++l) {
+        if (h->kind[l] == KIND_COL) col_P = std::max<int64_t>(col_P, layer_P(h->hlc[l]));
+        else all_col = false;
     }
-    if ((e = hipMalloc(&h->slab, h->slab_bytes)) != hipSuccess)
+    if (all_col) col_P = std::max<int64_t>(col_P, h->P);
+    const size_t row = std::max<size_t>((size_t)col_P * h->esize, (size_t)(kan::kMaxGrid + 2) * sizeof(double));
+    if ((e = h->slab.reserve((size_t)kSlabBlocks * row)) != hipSuccess)
         return bail(fail(h, KANODE_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)));
     *out = h;
     return KANODE_OK;
@@ -1011,20 +992,8 @@ kanode_status kanode_create(const kanode_spec* spec, kanode_handle** out) {
 void kanode_destroy(kanode_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->spec.device);
-    if (h->dlc) (void)hipFree(h->dlc);
-    if (h->slab) (void)hipFree(h->slab);
-    if (h->ws) (void)hipFree(h->ws);
-    if (h->stage) (void)hipFree(h->stage);
-    if (h->dpc) (void)hipFree(h->dpc);
-    if (h->stage_ws) (void)hipFree(h->stage_ws);
-    if (h->dtable) (void)hipFree(h->dtable);
-    if (h->defer_slab) (void)hipFree(h->defer_slab);
-    if (h->cstep_slab) (void)hipFree(h->cstep_slab);
-    if (h->step_slab) (void)hipFree(h->step_slab);
-    if (h->fin_ctr) (void)hipFree(h->fin_ctr);
-    if (h->train_buf) (void)hipFree(h->train_buf);
     if (h->solve_cache) kanode_solution_free(h->solve_cache);
-    delete h;
+    delete h;   // (its buffers free themselves)
 }
 
 int64_t kanode_param_length(const kanode_handle* h) { return h ? h->P : -1; }
@@ -1047,20 +1016,15 @@ kanode_status kanode_reserve(kanode_handle* h, int64_t max_batch) {
     s = ensure_ws(h, max_batch, nullptr);
     if (s != KANODE_OK) return s;
     if (h->spec.rhs_kind == KANODE_RHS_POINTWISE_PERIODIC_LAPLACIAN) {
-        const size_t need = (size_t)(h->spec.nx * max_batch) * h->esize;
-        if (need > h->ws_bytes) {
-            HIP_TRY(h, hipDeviceSynchronize());
-            if (h->ws) HIP_TRY(h, hipFree(h->ws));
-            HIP_TRY(h, hipMalloc(&h->ws, need));
-            h->ws_bytes = need;
-        }
+        if ((size_t)(h->spec.nx * max_batch) * h->esize > h->ws.bytes()) HIP_TRY(h, hipDeviceSynchronize());   // (every stream)
+        if ((s = ensure_fk_ws(h, max_batch, nullptr)) != KANODE_OK) return s;
     }
     // Reset the table stamps: re-zeroing the stamp region here (the call before graph capture / a
     // new batch) invalidates every build block's stamp, so the next launch rebuilds every table.
-    if (h->dtable) {
+    if (h->dtable()) {
         const int64_t off = (int64_t)kan::kPPMaxFns * kan::kPPCoef * h->hpc.ni;
         HIP_TRY(h, hipDeviceSynchronize());
-        HIP_TRY(h, hipMemset(h->dtable + off, 0, sizeof(double) * (size_t)(kan::pp_tables_doubles(h->hpc.ni) - off)));
+        HIP_TRY(h, hipMemset(h->dtable() + off, 0, sizeof(double) * (size_t)(kan::pp_tables_doubles(h->hpc.ni) - off)));
     }
     h->reserved_batch = std::max(h->reserved_batch, max_batch);
     return KANODE_OK;
@@ -1209,12 +1173,7 @@ kanode_status kanode_vjp(kanode_handle* h, const void* p, const void* u, const v
 }
 
 static kanode_status stage_alloc(kanode_handle* h, size_t bytes) {
-    if (bytes <= h->stage_bytes) return KANODE_OK;
-    if (h->stage) HIP_TRY(h, hipFree(h->stage));
-    h->stage = nullptr;
-    h->stage_bytes = 0;
-    HIP_TRY(h, hipMalloc(&h->stage, bytes));
-    h->stage_bytes = bytes;
+    HIP_TRY(h, h->stage.reserve(bytes));
     return KANODE_OK;
 }
 
@@ -1225,7 +1184,7 @@ kanode_status kanode_rhs_host(kanode_handle* h, const void* p, const void* u, vo
     const size_t bp = (size_t)h->P * h->esize, bu = (size_t)(h->n_in * batch) * h->esize,
                  bo = (size_t)(h->n_out * batch) * h->esize;
     if ((s = stage_alloc(h, bp + bu + bo)) != KANODE_OK) return s;
-    char* d = (char*)h->stage;
+    char* d = (char*)h->stage.ptr();
     HIP_TRY(h, hipMemcpy(d, p, bp, hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(d + bp, u, bu, hipMemcpyHostToDevice));
     if ((s = kanode_rhs(h, d, d + bp, d + bp + bu, batch, nullptr)) != KANODE_OK) return s;
@@ -1241,7 +1200,7 @@ kanode_status kanode_vjp_host(kanode_handle* h, const void* p, const void* u, co
     const size_t bp = (size_t)h->P * h->esize, bu = (size_t)(h->n_in * batch) * h->esize,
                  bo = (size_t)(h->n_out * batch) * h->esize;
     if ((s = stage_alloc(h, 2 * bp + 2 * bu + bo)) != KANODE_OK) return s;
-    char* d = (char*)h->stage;
+    char* d = (char*)h->stage.ptr();
     char* dp_d = d + bp;
     char* u_d = dp_d + bp;
     char* lam_d = u_d + bu;
@@ -1324,10 +1283,10 @@ kanode_status kanode_edge_activations(kanode_handle* h, int32_t layer, const voi
     hipStream_t st = (hipStream_t)stream;
     if (h->hlc[layer].O > 64) return fail(h, KANODE_ERR_UNSUPPORTED, "edge activations need out_dims <= 64");
     if (h->spec.dtype == KANODE_F64) {
-        HIP_TRY(h, kan::launch_kd_edge_act<double>(h->hlc[layer], h->dlc + layer, (const double*)p_layer - off,
+        HIP_TRY(h, kan::launch_kd_edge_act<double>(h->hlc[layer], h->dlc() + layer, (const double*)p_layer - off,
                                                    (const double*)x, (double*)act, K, st));
     } else {
-        HIP_TRY(h, kan::launch_kd_edge_act<float>(h->hlc[layer], h->dlc + layer, (const float*)p_layer - off,
+        HIP_TRY(h, kan::launch_kd_edge_act<float>(h->hlc[layer], h->dlc() + layer, (const float*)p_layer - off,
                                                   (const float*)x, (float*)act, K, st));
     }
     return KANODE_OK;
@@ -1343,12 +1302,12 @@ kanode_status kanode_edge_scores(kanode_handle* h, int32_t layer, const void* p_
     const int64_t off = h->hlc[layer].p_off;
     hipStream_t st = (hipStream_t)stream;
     if (h->spec.dtype == KANODE_F64) {
-        HIP_TRY(h, kan::launch_kd_edge_scores<double>(h->hlc[layer], h->dlc + layer, (const double*)p_layer - off,
-                                                      (const double*)x, (double*)scores, (double*)h->slab,
-                                                      h->slab_bytes, K, st));
+        HIP_TRY(h, kan::launch_kd_edge_scores<double>(h->hlc[layer], h->dlc() + layer, (const double*)p_layer - off,
+                                                      (const double*)x, (double*)scores, (double*)h->slab.ptr(),
+                                                      h->slab.bytes(), K, st));
     } else {
-        HIP_TRY(h, kan::launch_kd_edge_scores<float>(h->hlc[layer], h->dlc + layer, (const float*)p_layer - off,
-                                                     (const float*)x, (float*)scores, (float*)h->slab, h->slab_bytes,
+        HIP_TRY(h, kan::launch_kd_edge_scores<float>(h->hlc[layer], h->dlc() + layer, (const float*)p_layer - off,
+                                                     (const float*)x, (float*)scores, (float*)h->slab.ptr(), h->slab.bytes(),
                                                      K, st));
     }
     return KANODE_OK;
@@ -1382,7 +1341,7 @@ kanode_status kanode_adam_step(void* x, void* m, void* v, const void* g, int64_t
 
 }  // extern "C"
 
-// ---- internal entry points for the integrator (kanode_solve.cpp) ----------------
+// ---- internal entry points for the integrator (kanode_solve.cpp, kanode_adjoint.cpp, kanode_train.cpp) ----
 kanode_status kanode_internal_fail(kanode_handle* h, kanode_status s, const std::string& msg) { return fail(h, s, msg); }
 int kanode_internal_dtype(const kanode_handle* h) { return h->spec.dtype; }
 int64_t kanode_internal_state_length(const kanode_handle* h) { return h->n_in; }
@@ -1391,7 +1350,7 @@ void kanode_internal_hold_tables(kanode_handle* h, bool on) {
     h->hold_tables = on;
     h->built_phi = h->built_vjp = false;
 }
-double* kanode_internal_scratch(kanode_handle* h) { return (double*)h->slab; }
+double* kanode_internal_scratch(kanode_handle* h) { return (double*)h->slab.ptr(); }
 void* kanode_internal_solution_cache(kanode_handle* h) { return &h->solve_cache; }
 int kanode_internal_scratch_rows(const kanode_handle*) { return kSlabBlocks; }
 kanode_status kanode_internal_check(kanode_handle* h) { return check_handle(h); }
@@ -1437,12 +1396,12 @@ kanode_status kanode_internal_fk_step_loop(kanode_handle* h, const void* p, cons
     const hipStream_t st = (hipStream_t)stream;
     if (table_build(h, h->built_phi)) {
         const int fn_phi = kan::PP_PHI;
-        HIP_TRY(h, kan::launch_fk_pp_build(h->hpc, h->dlc, h->dpc, (const double*)p, h->dtable, &fn_phi, 1, st));
+        HIP_TRY(h, kan::launch_fk_pp_build(h->hpc, h->dlc(), h->dpc(), (const double*)p, h->dtable(), &fn_phi, 1, st));
     }
     const double dx2 = h->spec.dx * h->spec.dx;
     const double cd = h->spec.diffusion * (-2.0 / dx2), co = h->spec.diffusion * (1.0 / dx2);
-    HIP_TRY(h, kan::launch_fk_step_pp_loop(h->hpc, h->hlc[0], h->dlc, cd, co, (int)h->spec.nx, (const double*)p,
-                                           h->dtable, *la, lq, batch, st, h->grid_ovr.rhs));
+    HIP_TRY(h, kan::launch_fk_step_pp_loop(h->hpc, h->hlc[0], h->dlc(), cd, co, (int)h->spec.nx, (const double*)p,
+                                           h->dtable(), *la, lq, batch, st, h->grid_ovr.rhs));
     return KANODE_OK;
 }
 kanode_status kanode_internal_fk_step(kanode_handle* h, const void* p, const void* u, const void* k1,
@@ -1455,10 +1414,10 @@ kanode_status kanode_internal_fk_step(kanode_handle* h, const void* p, const voi
     if (!kanode_internal_fk_step_ok(h)) return KANODE_OK;
     const double dx2 = h->spec.dx * h->spec.dx;
     const double cd = h->spec.diffusion * (-2.0 / dx2), co = h->spec.diffusion * (1.0 / dx2);
-    HIP_TRY(h, kan::launch_fk_step_pp(h->hpc, h->hlc[0], h->dlc, h->dpc, (const double*)p, h->dtable, cd, co,
+    HIP_TRY(h, kan::launch_fk_step_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), (const double*)p, h->dtable(), cd, co,
                                       (int)h->spec.nx, (const double*)u, (const double*)k1, (double* const*)kout,
                                       (double*)u_new, a6x6, e7, q4x7, abstol, reltol,
-                                      err_parts && nparts ? err_parts : (double*)h->slab, kSlabBlocks, err_out, batch,
+                                      err_parts && nparts ? err_parts : (double*)h->slab.ptr(), kSlabBlocks, err_out, batch,
                                       (hipStream_t)stream, table_build(h, h->built_phi), h->grid_ovr.rhs,
                                       err_parts && nparts ? nparts : nullptr));
     launched = true;
@@ -1493,10 +1452,10 @@ kanode_status kanode_internal_chain_step(kanode_handle* h, const void* p, const 
     const hipStream_t st = (hipStream_t)stream;
     const hipError_t e =
         h->spec.dtype == KANODE_F64
-            ? kan::launch_kd_chain_step<double>(h->hlc, h->n_layers, h->dlc, (const double*)p, h->P, batch, a,
-                                                (double*)h->slab, kSlabBlocks, err_out, st)
-            : kan::launch_kd_chain_step<float>(h->hlc, h->n_layers, h->dlc, (const float*)p, h->P, batch, a,
-                                               (double*)h->slab, kSlabBlocks, err_out, st);
+            ? kan::launch_kd_chain_step<double>(h->hlc, h->n_layers, h->dlc(), (const double*)p, h->P, batch, a,
+                                                (double*)h->slab.ptr(), kSlabBlocks, err_out, st)
+            : kan::launch_kd_chain_step<float>(h->hlc, h->n_layers, h->dlc(), (const float*)p, h->P, batch, a,
+                                               (double*)h->slab.ptr(), kSlabBlocks, err_out, st);
     if (e == hipErrorNotSupported) return KANODE_OK;
     if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_step: ") + hipGetErrorString(e));
     launched = true;
@@ -1509,23 +1468,19 @@ static kanode_status chain_adjoint_step_t(kanode_handle* h, const T* p, const ka
                                           void* const* km_out, double* err_out, int64_t batch, hipStream_t st,
                                           bool& launched) {
     const size_t row = (size_t)h->P * sizeof(T) + sizeof(double);
-    int64_t cap = (int64_t)(h->slab_bytes / row) - 1;   // the stage kernel's grid cap (launch_kd_chain_vjp_stage)
+    int64_t cap = (int64_t)(h->slab.bytes() / row) - 1;   // the stage kernel's grid cap (launch_kd_chain_vjp_stage)
     if (cap > 1024) cap = 1024;
     if (cap < 1) return KANODE_OK;
     const size_t need = kan::chain_vjp_step_slab_bytes(h->P, batch, sizeof(T), (int)cap);
-    if (h->cstep_bytes < need) {
+    if (h->cstep_slab.bytes() < need) {
         if (is_capturing(st)) return fail(h, KANODE_ERR_CAPTURE, "chain adjoint step slab grows during capture");
         HIP_TRY(h, hipStreamSynchronize(st));
-        if (h->cstep_slab) HIP_TRY(h, hipFree(h->cstep_slab));
-        h->cstep_slab = nullptr;
-        h->cstep_bytes = 0;
-        HIP_TRY(h, hipMalloc(&h->cstep_slab, need));
-        h->cstep_bytes = need;
+        HIP_TRY(h, h->cstep_slab.reserve(need));
     }
     T* km[7];
     for (int s = 0; s < (a.fsal ? 7 : 6); ++s) km[s] = (T*)km_out[s];
-    const hipError_t e = kan::launch_kd_chain_vjp_step<T>(h->hlc, h->n_layers, h->dlc, p, h->P, batch, a, (int)cap,
-                                                          h->cstep_slab, h->cstep_bytes, km, err_out, st);
+    const hipError_t e = kan::launch_kd_chain_vjp_step<T>(h->hlc, h->n_layers, h->dlc(), p, h->P, batch, a, (int)cap,
+                                                          h->cstep_slab.ptr(), h->cstep_slab.bytes(), km, err_out, st);
     if (e == hipErrorNotSupported) return KANODE_OK;
     if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_vjp_step: ") + hipGetErrorString(e));
     launched = true;
@@ -1536,7 +1491,7 @@ bool kanode_internal_chain_adjoint_step_ok(const kanode_handle* h) {
     for (int l = 0; l < h->n_layers; ++l)
         if (h->kind[l] != KIND_COL) return false;
     const size_t esize = h->spec.dtype == KANODE_F64 ? sizeof(double) : sizeof(float);
-    if ((int64_t)(h->slab_bytes / ((size_t)h->P * esize + sizeof(double))) - 1 < 1) return false;
+    if ((int64_t)(h->slab.bytes() / ((size_t)h->P * esize + sizeof(double))) - 1 < 1) return false;
     return kan::chain_vjp_step_supported(h->hlc, h->n_layers, h->P, esize);
 }
 kanode_status kanode_internal_chain_adjoint_step(kanode_handle* h, const void* p, const void* args, void* const* km_out,
@@ -1560,7 +1515,7 @@ kanode_status kanode_internal_fk_adjoint_loop_geometry(kanode_handle* h, int64_t
         kan::fk_adjoint_loop_grid(batch, kSlabBlocks / 2) < 1)
         return KANODE_OK;
     if (kanode_status s = ensure_adjoint_slabs(h, (hipStream_t)stream); s != KANODE_OK) return s;
-    *slab = (double*)h->step_slab;
+    *slab = (double*)h->step_slab.ptr();
     *grid = kan::fk_adjoint_loop_grid(batch, kSlabBlocks / 2);
     ok = true;
     return KANODE_OK;
@@ -1569,7 +1524,7 @@ kanode_status kanode_internal_fk_adjoint_loop(kanode_handle* h, const void* p, c
                                               int64_t batch, void* stream) {
     const double dx2 = h->spec.dx * h->spec.dx;
     const double cd = h->spec.diffusion * (-2.0 / dx2), co = h->spec.diffusion * (1.0 / dx2);
-    HIP_TRY(h, kan::launch_fk_adjoint_loop(h->hpc, h->hlc[0], h->dlc, h->dpc, (const double*)p, h->dtable, cd, co,
+    HIP_TRY(h, kan::launch_fk_adjoint_loop(h->hpc, h->hlc[0], h->dlc(), h->dpc(), (const double*)p, h->dtable(), cd, co,
                                            (int)h->spec.nx, *la, batch, (hipStream_t)stream,
                                            table_build(h, h->built_vjp)));
     return KANODE_OK;
@@ -1588,12 +1543,12 @@ kanode_status kanode_internal_fk_adjoint_step(kanode_handle* h, const void* p, k
     if (kanode_status s = ensure_adjoint_slabs(h, st); s != KANODE_OK) return s;
     const double dx2 = h->spec.dx * h->spec.dx;
     const double cd = h->spec.diffusion * (-2.0 / dx2), co = h->spec.diffusion * (1.0 / dx2);
-    a->err_slab = err_out ? (double*)h->step_slab : nullptr;   // relocated by the launcher
+    a->err_slab = err_out ? (double*)h->step_slab.ptr() : nullptr;   // relocated by the launcher
     int grid = 0, comb = 0;
     a->combine = err_out && af ? 2 : (combined != nullptr && err_out == nullptr ? 1 : 0);
     a->fin_ctr = nullptr;
     if (err_out && af && h->adj_fused_finish) {   // the finish inside the rows kernel (the launcher may decline)
-        a->fin_ctr = h->fin_ctr;
+        a->fin_ctr = h->fin_ctr.as<unsigned>();
         a->fin = kan::AdjFinish{};
         a->fin.a0 = af->a6[0];
         a->fin.e0 = af->bt[0];
@@ -1606,11 +1561,11 @@ kanode_status kanode_internal_fk_adjoint_step(kanode_handle* h, const void* p, k
         a->fin.out = af->out;
         // the arrival counters re-zeroed on the stream before every fused launch: a wait that timed
         // out in an earlier launch cannot leave them off by one for this one
-        HIP_TRY(h, hipMemsetAsync(h->fin_ctr, 0, 2 * sizeof(unsigned), st));
+        HIP_TRY(h, hipMemsetAsync(h->fin_ctr.ptr(), 0, 2 * sizeof(unsigned), st));
     }
     bool fused_fin = false;
-    HIP_TRY(h, kan::launch_fk_vjp_step_pp(h->hpc, h->hlc[0], h->dlc, h->dpc, (const double*)p, h->dtable, cd, co,
-                                          (int)h->spec.nx, *a, (double*)h->step_slab, kSlabBlocks / 2, batch, &grid, st,
+    HIP_TRY(h, kan::launch_fk_vjp_step_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), (const double*)p, h->dtable(), cd, co,
+                                          (int)h->spec.nx, *a, (double*)h->step_slab.ptr(), kSlabBlocks / 2, batch, &grid, st,
                                           table_build(h, h->built_vjp), h->grid_ovr.vstep,
                                           h->grid_ovr.vstep_rows, &comb, &fused_fin));
     if (fused_fin) {   // μ_new, kμ_7 and the error terms are written by the step kernel itself
@@ -1619,7 +1574,7 @@ kanode_status kanode_internal_fk_adjoint_step(kanode_handle* h, const void* p, k
         return KANODE_OK;
     }
     kan::FinishJobs jobs{};
-    double* base = (double*)h->step_slab;
+    double* base = (double*)h->step_slab.ptr();
     if (comb == 1) {
         // km[0] <- Σ_{s<5} h·a6_{s+1}·kμ_{s+2} (the kernel's combined rows), km[5] <- kμ_7
         for (int q = 0; q < 2; ++q) {
@@ -1705,8 +1660,8 @@ kanode_status kanode_internal_chain_adjoint(kanode_handle* h, const void* p, int
     if (fk_small_ok(h, batch)) {
         const int fns[2] = {kan::PP_DPHI, kan::PP_SWISH};
         if (table_build(h, h->built_vjp))
-            HIP_TRY(h, kan::launch_fk_pp_build(h->hpc, h->dlc, h->dpc, (const double*)p, h->dtable, fns, 2, st));
-        const hipError_t e = kan::launch_fk_small_adjoint(h->hlc[0], h->hpc, h->dlc, (const double*)p, h->dtable,
+            HIP_TRY(h, kan::launch_fk_pp_build(h->hpc, h->dlc(), h->dpc(), (const double*)p, h->dtable(), fns, 2, st));
+        const hipError_t e = kan::launch_fk_small_adjoint(h->hlc[0], h->hpc, h->dlc(), (const double*)p, h->dtable(),
                                                           fk_small_args(h), batch, *a, st);
         if (e == hipErrorNotSupported) return KANODE_OK;
         if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_fk_small_adjoint: ") + hipGetErrorString(e));
@@ -1715,9 +1670,9 @@ kanode_status kanode_internal_chain_adjoint(kanode_handle* h, const void* p, int
     }
     const hipError_t e =
         h->spec.dtype == KANODE_F64
-            ? kan::launch_kd_chain_adjoint<double>(h->hlc, h->n_layers, h->dlc, (const double*)p, h->P, batch, *a, st,
+            ? kan::launch_kd_chain_adjoint<double>(h->hlc, h->n_layers, h->dlc(), (const double*)p, h->P, batch, *a, st,
                                                    h->chain_wide)
-            : kan::launch_kd_chain_adjoint<float>(h->hlc, h->n_layers, h->dlc, (const float*)p, h->P, batch, *a, st,
+            : kan::launch_kd_chain_adjoint<float>(h->hlc, h->n_layers, h->dlc(), (const float*)p, h->P, batch, *a, st,
                                                   h->chain_wide);
     if (e == hipErrorNotSupported) return KANODE_OK;
     if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_adjoint: ") + hipGetErrorString(e));
@@ -1733,17 +1688,13 @@ bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch) {
 static kanode_status train_buf_stage(kanode_handle* h, size_t off_meta, const std::vector<char>& meta, hipStream_t st,
                                      char*& base) {
     const size_t need = off_meta + meta.size() + 64;
-    if (h->train_bytes < need) {
+    if (h->train_buf.bytes() < need) {
         HIP_TRY(h, hipStreamSynchronize(st));
-        if (h->train_buf) HIP_TRY(h, hipFree(h->train_buf));
-        h->train_buf = nullptr;
-        h->train_bytes = 0;
-        h->train_meta.clear();
+        h->train_meta.clear();   // (its device copy goes)
         h->train_meta_off = 0;
-        HIP_TRY(h, hipMalloc(&h->train_buf, need));
-        h->train_bytes = need;
+        HIP_TRY(h, h->train_buf.reserve(need));
     }
-    base = (char*)h->train_buf;
+    base = (char*)h->train_buf.ptr();
     if (h->train_meta != meta || h->train_meta_off != off_meta) {
         // (the earlier calls synchronised, so nothing on the device still reads the old bytes)
         HIP_TRY(h, hipMemcpy(base + off_meta, meta.data(), meta.size(), hipMemcpyHostToDevice));
@@ -1768,25 +1719,15 @@ kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs*
         }
         cap = lo >= 64 ? lo : kan::kChainAdjointMaxSteps;
     }
-    if (!a->adaptive && h->fused_solve_cap < 1) {   // fixed steps: exactly the steps of the solve (solve_fused_t's count)
-        int64_t n = 0;
-        for (double t = a->t0, dt = a->dt;
-             n < kan::kChainAdjointMaxSteps && !(t >= a->tf - 1e-14 * std::max(1.0, std::fabs(a->tf))); ++n) {
-            dt = std::min(dt, a->tf - t);
-            t = t + dt;
-        }
-        cap = std::max<int64_t>(n, 1);
-    }
+    if (!a->adaptive && h->fused_solve_cap < 1)   // fixed steps: exactly the steps of the solve (solve_fused_t's count)
+        cap = std::max<int64_t>(kanode_fixed_step_count(a->t0, a->tf, a->dt, kan::kChainAdjointMaxSteps), 1);
     int stage_rec = 0;
     if (!kan::chain_train_lds(cap, a->n_save, a->n_save_test, &stage_rec))
         return fail(h, KANODE_ERR_UNSUPPORTED, "kanode_train_tsit5: not supported (saveat lists too long for one workgroup's LDS)");
     const size_t off_rec = 64;
     const size_t off_meta = off_rec + sizeof(double) * ((size_t)kan::kChainAdjointMaxSteps * 7 * 2 + 2);
     char* base = nullptr;
-    {
-        const kanode_status r = train_buf_stage(h, off_meta, meta, st, base);
-        if (r != KANODE_OK) return r;
-    }
+    if (const kanode_status r = train_buf_stage(h, off_meta, meta, st, base); r != KANODE_OK) return r;
     const double* md = (const double*)(base + off_meta);
     a->saveat = md;
     a->saveat_test = md + a->n_save;
@@ -1797,7 +1738,7 @@ kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs*
     a->stage_rec = stage_rec;
     a->rec = (double*)(base + off_rec);
     a->out = (int64_t*)base;
-    const hipError_t e = kan::launch_kd_chain_train(h->hlc, h->n_layers, h->dlc, h->P, *a, st);
+    const hipError_t e = kan::launch_kd_chain_train(h->hlc, h->n_layers, h->dlc(), h->P, *a, st);
     if (e == hipErrorNotSupported)
         return fail(h, KANODE_ERR_UNSUPPORTED, "kanode_train_tsit5: not supported (shape not covered by the training kernel)");
     if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_train: ") + hipGetErrorString(e));
@@ -1817,7 +1758,7 @@ kanode_status kanode_internal_pair_adjoint(kanode_handle* h, const void* p, int6
     a->P = h->P;
     a->max_wg = h->pair_persist_max_wg;
     a->force_abort = h->pair_persist_abort ? 1 : 0;
-    const hipError_t e = kan::launch_kd_pair_adjoint(h->hlc, h->dlc, (const double*)p, batch, *a, (hipStream_t)stream);
+    const hipError_t e = kan::launch_kd_pair_adjoint(h->hlc, h->dlc(), (const double*)p, batch, *a, (hipStream_t)stream);
     if (e == hipErrorNotSupported) return KANODE_OK;
     if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_kd_pair_adjoint: ") + hipGetErrorString(e));
     launched = true;
@@ -1832,12 +1773,12 @@ std::vector<double>* kanode_internal_adjoint_steps(kanode_handle* h) {
 
 extern "C" kanode_status kanode_table_rejections(kanode_handle* h, int32_t out[3]) {
     if (!h || !out) return KANODE_ERR_INVALID_ARG;
-    if (!h->dtable || !h->pp_on) return fail(h, KANODE_ERR_UNSUPPORTED, "no pointwise table on this handle");
+    if (!h->dtable() || !h->pp_on) return fail(h, KANODE_ERR_UNSUPPORTED, "no pointwise table on this handle");
     const int ni = h->hpc.ni, nb = ni / kan::kPPPerBlock;
     const int64_t off = (int64_t)kan::kPPMaxFns * kan::kPPCoef * ni;
     std::vector<double> st((size_t)kan::kPPMaxFns * nb * kan::kPPStampStride);
     HIP_TRY(h, hipDeviceSynchronize());
-    HIP_TRY(h, hipMemcpy(st.data(), h->dtable + off, st.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(st.data(), h->dtable() + off, st.size() * sizeof(double), hipMemcpyDeviceToHost));
     for (int f = 0; f < kan::kPPMaxFns; ++f) {
         int32_t n = 0;
         bool built = true;
@@ -1875,17 +1816,14 @@ kanode_status kanode_internal_fk_train(kanode_handle* h, int64_t batch, kan::Cha
     const size_t off_acc = 64;   // the accumulators of the two-entries-per-lane kernel (ChainTrainArgs::rec)
     const size_t off_meta = off_acc + sizeof(double) * (size_t)kan::kFsensMaxWaves * 2 * 64;
     char* base = nullptr;
-    {
-        const kanode_status r = train_buf_stage(h, off_meta, meta, st, base);
-        if (r != KANODE_OK) return r;
-    }
+    if (const kanode_status r = train_buf_stage(h, off_meta, meta, st, base); r != KANODE_OK) return r;
     const double* md = (const double*)(base + off_meta);
     a->saveat = md;
     a->saveat_test = md + a->n_save;
     a->rec = (double*)(base + off_acc);
     a->out = (int64_t*)base;
     const bool tab = h->pp_on && h->hpc.enabled;
-    const hipError_t e = kan::launch_fk_small_train(h->hlc[0], h->hpc, tab, h->dlc, h->dpc, fk_small_args(h), batch, *a,
+    const hipError_t e = kan::launch_fk_small_train(h->hlc[0], h->hpc, tab, h->dlc(), h->dpc(), fk_small_args(h), batch, *a,
                                                     h->fsens_wide, st);
     if (e == hipErrorNotSupported)
         return fail(h, KANODE_ERR_UNSUPPORTED, "kanode_train_forward_tsit5: not supported (shape or saveat lists not "
@@ -1901,10 +1839,10 @@ kanode_status kanode_internal_fk_fsens(kanode_handle* h, const void* p, const vo
     const bool tab = h->pp_on && h->hpc.enabled;
     if (tab) {
         const int fns[3] = {kan::PP_PHI, kan::PP_DPHI, kan::PP_SWISH};
-        HIP_TRY(h, kan::launch_fk_pp_build(h->hpc, h->dlc, h->dpc, (const double*)p, h->dtable, fns, 3, st));
+        HIP_TRY(h, kan::launch_fk_pp_build(h->hpc, h->dlc(), h->dpc(), (const double*)p, h->dtable(), fns, 3, st));
     }
-    const hipError_t e = kan::launch_fk_small_fsens(h->hlc[0], h->hpc, tab, h->dlc, (const double*)p,
-                                                    tab ? h->dtable : nullptr, fk_small_args(h), (const double*)u0,
+    const hipError_t e = kan::launch_fk_small_fsens(h->hlc[0], h->hpc, tab, h->dlc(), (const double*)p,
+                                                    tab ? h->dtable() : nullptr, fk_small_args(h), (const double*)u0,
                                                     batch, *a, (double*)s_save, h->fsens_wide, st);
     if (e == hipErrorNotSupported)
         return fail(h, KANODE_ERR_UNSUPPORTED, "forward sensitivities: shape not covered by the one-workgroup kernel");
@@ -1918,8 +1856,8 @@ kanode_status kanode_internal_chain_tsit5(kanode_handle* h, const void* p, const
     if (fk_small_ok(h, batch)) {
         const int fn = kan::PP_PHI;
         if (table_build(h, h->built_phi))
-            HIP_TRY(h, kan::launch_fk_pp_build(h->hpc, h->dlc, h->dpc, (const double*)p, h->dtable, &fn, 1, st));
-        const hipError_t e = kan::launch_fk_small_tsit5(h->hlc[0], h->hpc, h->dlc, (const double*)p, h->dtable,
+            HIP_TRY(h, kan::launch_fk_pp_build(h->hpc, h->dlc(), h->dpc(), (const double*)p, h->dtable(), &fn, 1, st));
+        const hipError_t e = kan::launch_fk_small_tsit5(h->hlc[0], h->hpc, h->dlc(), (const double*)p, h->dtable(),
                                                         fk_small_args(h), (const double*)u0, batch, *a, st);
         if (e == hipErrorNotSupported) return KANODE_OK;
         if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_fk_small_tsit5: ") + hipGetErrorString(e));
@@ -1928,9 +1866,9 @@ kanode_status kanode_internal_chain_tsit5(kanode_handle* h, const void* p, const
     }
     const hipError_t e =
         h->spec.dtype == KANODE_F64
-            ? kan::launch_kd_chain_tsit5<double>(h->hlc, h->n_layers, h->dlc, (const double*)p, h->P,
+            ? kan::launch_kd_chain_tsit5<double>(h->hlc, h->n_layers, h->dlc(), (const double*)p, h->P,
                                                  (const double*)u0, batch, *a, st)
-            : kan::launch_kd_chain_tsit5<float>(h->hlc, h->n_layers, h->dlc, (const float*)p, h->P, (const float*)u0,
+            : kan::launch_kd_chain_tsit5<float>(h->hlc, h->n_layers, h->dlc(), (const float*)p, h->P, (const float*)u0,
                                                 batch, *a, st);
     if (e == hipErrorNotSupported) return KANODE_OK;
     if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_tsit5: ") + hipGetErrorString(e));
@@ -1970,11 +1908,6 @@ kanode_status kanode_internal_prepare(kanode_handle* h, int64_t batch, hipStream
     kanode_status s = check_handle(h);
     if (s != KANODE_OK) return s;
     if ((s = ensure_ws(h, batch, st)) != KANODE_OK) return s;
-    if (h->spec.rhs_kind == KANODE_RHS_POINTWISE_PERIODIC_LAPLACIAN && h->ws_bytes < (size_t)(h->spec.nx * batch) * h->esize) {
-        HIP_TRY(h, hipStreamSynchronize(st));
-        if (h->ws) HIP_TRY(h, hipFree(h->ws));
-        HIP_TRY(h, hipMalloc(&h->ws, (size_t)(h->spec.nx * batch) * h->esize));
-        h->ws_bytes = (size_t)(h->spec.nx * batch) * h->esize;
-    }
+    if (h->spec.rhs_kind == KANODE_RHS_POINTWISE_PERIODIC_LAPLACIAN && (s = ensure_fk_ws(h, batch, st)) != KANODE_OK) return s;
     return ensure_stage_ws(h, 2 * (size_t)(h->n_in * batch) * h->esize, st);
 }

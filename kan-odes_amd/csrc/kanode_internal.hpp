@@ -1,9 +1,11 @@
 // kanode_internal.hpp — handle accessors shared between the C-ABI translation units
-// (kanode_abi.cpp owns the handle; kanode_solve.cpp is the integrator around it).
+// (kanode_abi.cpp owns the handle; kanode_solve.cpp, kanode_adjoint.cpp and kanode_train.cpp are the integrator around it).
 // C++ linkage, not part of the C-ABI.
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -19,6 +21,18 @@ struct AdjStepArgs;
 struct PairAdjArgs;
 struct FkLoopArgs;
 struct AdjLoopArgs;
+}
+
+// whether t has reached tf (the solvers' end test), and the steps a fixed-step solve takes up to max_steps (the
+// last one shortened to land on tf): the host's statement of what the one-launch kernels count themselves
+inline bool kanode_at_end(double t, double tf) { return t >= tf - 1e-14 * std::max(1.0, std::fabs(tf)); }
+inline int64_t kanode_fixed_step_count(double t0, double tf, double dt, int64_t max_steps) {
+    int64_t n = 0;
+    for (double t = t0; n < max_steps && !kanode_at_end(t, tf); ++n) {
+        dt = std::min(dt, tf - t);
+        t = t + dt;
+    }
+    return n;
 }
 
 kanode_status kanode_internal_fail(kanode_handle* h, kanode_status s, const std::string& msg);
