@@ -510,6 +510,53 @@ kanode_status kanode_train_forward_tsit5(kanode_handle* h, void* p, void* m, voi
                                          double* loss_test, void* grad, void* p_before, int64_t* counts,
                                          int64_t* iters_done, int32_t* stop_reason, void* stream);
 
+/* --- ensemble training: n_replicas independent device-resident loops in ONE launch --------------
+ * kanode_train_ensemble_tsit5 / kanode_train_forward_ensemble_tsit5 run the loop of kanode_train_tsit5 /
+ * kanode_train_forward_tsit5 on n_replicas (1 .. 4096) replicas of one problem at once, one workgroup per replica:
+ * seeds, learning rates or penalty weights side by side on compute units a single loop leaves idle.  Replica r
+ * computes, bit for bit, what its single-replica twin computes from the same p, m, v, eta, l1 and running powers;
+ * no replica reads another's data or waits for it.
+ *
+ * The arguments are the twin's, except:
+ *     p, m, v       device arrays [n_replicas][P], contiguous, the caller's, updated in place
+ *     eta           host array [n_replicas]
+ *     l1            host array [n_replicas] (finite, >= 0), or NULL for all zero: replica r's λ of the L1 term.  The
+ *                   forward entry refuses any non-zero entry (KANODE_ERR_UNSUPPORTED, nothing launched); the
+ *                   handle's kanode_set_l1_penalty value is not read by these calls
+ *     beta_t        host array [n_replicas][2]: replica r's running powers on entry; read only -- the caller
+ *                   advances its copy by iters_done[r] products
+ *     loss, loss_test [n_replicas][n_iters]; grad, p_before [n_replicas][n_iters][P]; counts [n_replicas][n_iters][4]
+ *                   device outputs with a leading replica dimension (nullable as the twin's)
+ *     iters_done, stop_reason   host arrays [n_replicas]
+ * u0, saveat, target, the test problem and the solver options are shared by all replicas and only read.  The
+ * per-replica status words, private blocks (the global dense output / the accumulators at two entries per lane)
+ * and argument structs, and ONE copy of the saveat lists and jump groups, live on the handle and are reused.
+ *
+ * The stop rule is the twin's, per replica: a failing iteration stops THAT replica before its Adam step, its p, m, v
+ * left as its last good iteration made them, iters_done[r] and stop_reason[r] (a kanode_train_stop) say where and
+ * why, and the other replicas run on.  The call synchronises the stream and returns KANODE_OK whenever the launch
+ * ran, even if some replica stopped; kanode_last_error then names the lowest stopped replica.
+ *
+ * Covered: exactly the shapes of kanode_train_supported / kanode_train_forward_supported.  Anything else:
+ * KANODE_ERR_UNSUPPORTED, nothing launched.  A capturing stream is refused (KANODE_ERR_CAPTURE). */
+kanode_status kanode_train_ensemble_tsit5(kanode_handle* h, int64_t n_replicas, void* p, void* m, void* v,
+                                          const void* u0, int64_t batch, double t0, double tf, const double* saveat,
+                                          int64_t n_save, const void* target, double tf_test,
+                                          const double* saveat_test, int64_t n_save_test, const void* target_test,
+                                          const kanode_solver_options* opt, const double* eta, const double* l1,
+                                          double beta1, double beta2, double eps, const double* beta_t,
+                                          int64_t n_iters, double* loss, double* loss_test, void* grad, void* p_before,
+                                          int64_t* counts, int64_t* iters_done, int32_t* stop_reason, void* stream);
+kanode_status kanode_train_forward_ensemble_tsit5(kanode_handle* h, int64_t n_replicas, void* p, void* m, void* v,
+                                                  const void* u0, int64_t batch, double t0, double tf,
+                                                  const double* saveat, int64_t n_save, const void* target,
+                                                  double tf_test, const double* saveat_test, int64_t n_save_test,
+                                                  const void* target_test, const kanode_solver_options* opt,
+                                                  const double* eta, const double* l1, double beta1, double beta2,
+                                                  double eps, const double* beta_t, int64_t n_iters, double* loss,
+                                                  double* loss_test, void* grad, void* p_before, int64_t* counts,
+                                                  int64_t* iters_done, int32_t* stop_reason, void* stream);
+
 /* --- the data-parallel gradient all-reduce (one process per GPU) -----------------
  * For hosts without a collective of their own (Julia, C): after kanode_adjoint_tsit5 on each rank's
  * trajectory shard, the flat [dp; L] is SUM all-reduced in place over RCCL (xGMI inside a node), then

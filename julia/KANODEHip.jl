@@ -514,6 +514,66 @@ function train_forward_tsit5!(h::Handle, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cv
     return done[], stop[]
 end
 
+# --- ensemble training (kanode_train_ensemble_tsit5 / kanode_train_forward_ensemble_tsit5): R independent replicas
+# of one problem in one launch, one workgroup each.  p, m, v are device pointers to R x P arrays (replica-major:
+# Julia's P x R), the outputs carry a leading replica dimension (loss: n_iters x R in Julia's order); η, l1 and βp
+# are host vectors of R entries (βp: R pairs).  A replica that stops does not throw: the returned vectors say which
+# replicas stopped and why (kanode_train_stop); the others run on.
+function train_ensemble_call(name::Symbol, h::Handle, R::Integer, p, m, v, u0, B::Integer, tspan,
+                             saveat::Vector{Float64}, target, n_iters::Integer, loss, η, l1, β, ϵ, βp, test,
+                             loss_test, grad, p_before, counts, opt::SolverOptions, stream)
+    issorted(saveat) || throw(ArgumentError("saveat must be ascending"))
+    ηv = η isa Real ? fill(Float64(η), R) : Vector{Float64}(η)
+    l1v = l1 === nothing ? Float64[] : Vector{Float64}(l1)
+    βv = βp === nothing ? repeat(Float64[β[1], β[2]], R) : Float64[x for pair in βp for x in pair]
+    (length(ηv) == R && length(βv) == 2R && (l1 === nothing || length(l1v) == R)) ||
+        throw(DimensionMismatch("η, l1 and βp need one entry per replica"))
+    tf_t, sv_t, tg_t = test === nothing ? (0.0, Float64[], Ptr{Cvoid}(C_NULL)) : (Float64(test[1]), Vector{Float64}(test[2]), test[3])
+    done = zeros(Int64, R)
+    stop = zeros(Int32, R)
+    st = GC.@preserve saveat sv_t ηv l1v βv done stop ccall(sym(name), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float64}, Int64,
+         Ptr{Cvoid}, Float64, Ptr{Float64}, Int64, Ptr{Cvoid}, Ref{SolverOptions}, Ptr{Float64}, Ptr{Float64}, Float64,
+         Float64, Float64, Ptr{Float64}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64},
+         Ptr{Int32}, Ptr{Cvoid}),
+        h.ptr, R, p, m, v, u0, B, tspan[1], tspan[2], saveat, length(saveat), target, tf_t, sv_t, length(sv_t), tg_t,
+        opt, ηv, l1 === nothing ? Ptr{Float64}(C_NULL) : pointer(l1v), β[1], β[2], ϵ, βv, n_iters, loss, loss_test,
+        grad, p_before, counts, done, stop, stream)
+    check(h, st)
+    return done, stop
+end
+
+"""train_ensemble_tsit5!(h, R, p, m, v, u0, tspan, saveat, target, n_iters, loss; η, l1, β, ϵ, βp, test, loss_test,
+grad, p_before, counts, opt) -> (iters_done, stop_reason), vectors of R: train_tsit5! on R replicas at once.  η and
+l1 are a number or R of them (l1 = nothing: no penalty; the handle's set_l1_penalty! value is not read), βp R pairs of
+running powers (nothing: a fresh optimiser); advance replica r's by iters_done[r] products afterwards."""
+function train_ensemble_tsit5!(h::Handle, R::Integer, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cvoid}, u0::Ptr{Cvoid},
+                               tspan, saveat::Vector{Float64}, target::Ptr{Cvoid}, n_iters::Integer, loss::Ptr{Cvoid};
+                               η = 1e-3, l1 = nothing, β = (0.9, 0.999), ϵ::Real = 1e-8, βp = nothing, test = nothing,
+                               loss_test::Ptr{Cvoid} = C_NULL, grad::Ptr{Cvoid} = C_NULL,
+                               p_before::Ptr{Cvoid} = C_NULL, counts::Ptr{Cvoid} = C_NULL,
+                               opt::SolverOptions = default_options(), stream::Ptr{Cvoid} = C_NULL)
+    train_supported(h, 1) || throw(ArgumentError("train_ensemble_tsit5!: not covered for this handle"))
+    l1v = l1 isa Real ? fill(Float64(l1), R) : l1
+    return train_ensemble_call(:kanode_train_ensemble_tsit5, h, R, p, m, v, u0, 1, tspan, saveat, target, n_iters, loss,
+                               η, l1v, β, ϵ, βp, test, loss_test, grad, p_before, counts, opt, stream)
+end
+
+"""train_forward_ensemble_tsit5!(h, R, p, m, v, u0, B, tspan, saveat, target, n_iters, loss; ...) ->
+(iters_done, stop_reason): train_forward_tsit5! on R replicas at once (no L1 term)."""
+function train_forward_ensemble_tsit5!(h::Handle, R::Integer, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cvoid},
+                                       u0::Ptr{Cvoid}, B::Integer, tspan, saveat::Vector{Float64}, target::Ptr{Cvoid},
+                                       n_iters::Integer, loss::Ptr{Cvoid}; η = 1e-2, β = (0.9, 0.999), ϵ::Real = 1e-8,
+                                       βp = nothing, test = nothing, loss_test::Ptr{Cvoid} = C_NULL,
+                                       grad::Ptr{Cvoid} = C_NULL, p_before::Ptr{Cvoid} = C_NULL,
+                                       counts::Ptr{Cvoid} = C_NULL, opt::SolverOptions = default_options(),
+                                       stream::Ptr{Cvoid} = C_NULL)
+    train_forward_supported(h, B, test !== nothing) ||
+        throw(ArgumentError("train_forward_ensemble_tsit5!: not covered for this handle"))
+    return train_ensemble_call(:kanode_train_forward_ensemble_tsit5, h, R, p, m, v, u0, B, tspan, saveat, target,
+                               n_iters, loss, η, nothing, β, ϵ, βp, test, loss_test, grad, p_before, counts, opt, stream)
+end
+
 # --- pruning a sparsified KAN (LV_driver_KANODE.jl:52-108): per-edge scores on the device, the keep rule and the
 # parameter slicing on the host.  Scores are Julia [O, I] matrices (the memory kanode_edge_scores writes).
 layer_length(h::Handle, i::Integer) = Int(ccall(sym(:kanode_layer_param_length), Int64, (Ptr{Cvoid}, Int32), h.ptr, i))

@@ -1,0 +1,69 @@
+// kan_ensemble.hpp — the host side of an ensemble launch of the device-resident training loops (host only, no
+// HIP): where each replica's blocks lie in the handle's training buffer, and the per-replica argument structs.
+//
+// The buffer of a launch of R replicas:
+//     out [R][2] int64 | rec [R][rec_stride bytes] | args [R] | meta | 64 spare bytes
+// every block at a multiple of 64 bytes.  out[r] are replica r's status words (iterations done, stop reason), rec
+// its private block (the LV loop's global dense output, the Fisher-KPP loop's accumulators; rec_bytes = 0 where the
+// kernel keeps them in LDS), args the structs the workgroups read, meta the ONE copy of what all replicas share
+// (saveat lists, jump groups).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace kan {
+
+struct EnsembleLayout {
+    size_t off_rec, rec_stride, off_args, off_meta;
+};
+inline size_t ensemble_round(size_t bytes) { return (bytes + 63) & ~(size_t)63; }
+inline EnsembleLayout ensemble_layout(int64_t R, size_t rec_bytes, size_t arg_bytes) {
+    EnsembleLayout L;
+    L.off_rec = ensemble_round((size_t)R * 2 * sizeof(int64_t));
+    L.rec_stride = ensemble_round(rec_bytes);
+    L.off_args = L.off_rec + (size_t)R * L.rec_stride;
+    L.off_meta = ensemble_round(L.off_args + (size_t)R * arg_bytes);
+    return L;
+}
+// the bytes the buffer needs for this layout and a meta block of meta_bytes
+inline size_t ensemble_bytes(const EnsembleLayout& L, size_t meta_bytes) { return L.off_meta + meta_bytes + 64; }
+
+// What differs between the replicas, as the C entry points receive it: p, m, v [R][P] and the outputs with their
+// leading replica dimension are device arrays (the record pointers nullable), eta [R], l1 [R] (nullable: all zero)
+// and beta_t [R][2] host arrays.
+struct EnsembleReplicas {
+    int64_t R, P, n_iters;
+    double *p, *m, *v;
+    const double *eta, *l1, *beta_t;
+    double *loss, *loss_test, *grad, *p_before;
+    int64_t* counts;
+};
+
+// args[r] = shared with replica r's own fields set; base is the DEVICE address of the buffer laid out by L
+// (only offsets are formed from it, nothing is read through it).  Args: kan::ChainTrainArgs.
+template <class Args>
+void ensemble_fill_args(const Args& shared, const EnsembleReplicas& e, const EnsembleLayout& L, char* base,
+                        Args* args) {
+    const size_t P = (size_t)e.P, K = (size_t)e.n_iters;
+    for (int64_t r = 0; r < e.R; ++r) {
+        Args& a = args[r];
+        const size_t q = (size_t)r;
+        a = shared;
+        a.p = e.p + q * P;
+        a.m = e.m + q * P;
+        a.v = e.v + q * P;
+        a.eta = e.eta[r];
+        a.act_reg = e.l1 ? e.l1[r] : 0.0;
+        a.bp1 = e.beta_t[2 * r];
+        a.bp2 = e.beta_t[2 * r + 1];
+        a.loss = e.loss + q * K;
+        a.loss_test = shared.loss_test ? e.loss_test + q * K : nullptr;
+        a.grad = e.grad ? e.grad + q * K * P : nullptr;
+        a.p_before = e.p_before ? e.p_before + q * K * P : nullptr;
+        a.counts = e.counts ? e.counts + q * K * 4 : nullptr;
+        a.rec = L.rec_stride ? reinterpret_cast<double*>(base + L.off_rec + q * L.rec_stride) : nullptr;
+        a.out = reinterpret_cast<int64_t*>(base) + 2 * q;
+    }
+}
+
+}  // namespace kan

@@ -513,6 +513,13 @@ bool chain_train_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B,
 size_t chain_train_lds(int64_t cap, int64_t n_save, int64_t n_save_test, int* stage_rec);
 hipError_t launch_kd_chain_train(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P,
                                  const ChainTrainArgs& a, hipStream_t st);
+// The ensemble entries of both loops: n_rep independent replicas in one launch, workgroup r on args[r] (a device
+// array; `a` is the host copy of any one struct: the replicas differ only in p, m, v, eta, act_reg, bp1 / bp2, rec,
+// out and the record pointers).  No workgroup reads another's data or waits for it.
+constexpr int64_t kTrainMaxReplicas = 4096;
+hipError_t launch_kd_chain_train_ensemble(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P,
+                                          const ChainTrainArgs& a, const ChainTrainArgs* args, int64_t n_rep,
+                                          hipStream_t st);
 // K whole training iterations of a small Fisher-KPP field on the forward-mode gradient in ONE launch
 // (fk_small_train_kernel, kan_small_train.hip; Fisher-KPP_Source.jl:194-213): per iteration the tables at p_it
 // (pp_build_block, with tab), the Dual solve of fk_small_fsens_kernel with loss[it] and the gradient accumulated at
@@ -528,6 +535,9 @@ bool fk_small_train_supported(const LayerConst& hlc, const PPConst& hpc, bool ta
 hipError_t launch_fk_small_train(const LayerConst& hlc, const PPConst& hpc, bool tab, const LayerConst* lc,
                                  const PPConst* pc, const FkSmallArgs& s, int64_t B, const ChainTrainArgs& a, int wide,
                                  hipStream_t st);
+hipError_t launch_fk_small_train_ensemble(const LayerConst& hlc, const PPConst& hpc, bool tab, const LayerConst* lc,
+                                          const PPConst* pc, const FkSmallArgs& s, int64_t B, const ChainTrainArgs& a,
+                                          const ChainTrainArgs* args, int64_t n_rep, int wide, hipStream_t st);
 // A whole InterpolatingAdjoint step of a small chain per trajectory column (kd_chain_vjp_step_kernel, kan_col.hip):
 // the six adjoint stages of kanode_solve.cpp adjoint_t in one launch, λ and kλ_1..kλ_7 of a column in registers.
 // Stage s reads the forward dense output u_i + Σ_q su_c[s][q] k_{i,q} (K form, the forward step holding stage s)

@@ -87,10 +87,11 @@ __device__ __forceinline__ double wave_mse_lds(const double* __restrict__ us, co
     return __ddiv_rn(wave_sum(s), (double)cnt);
 }
 
+// (the loop of one replica: the body of both entry kernels below; it reads no block index)
 template <int NORM, int GT, bool TAB, int E, bool TEST>
-__global__ void __launch_bounds__((GT + 2) * kWave)
-fk_small_train_kernel(const LayerConst* __restrict__ lcp, const PPConst* __restrict__ pcp, FkSmallArgs s, int64_t B,
-                      ChainTrainArgs a) {
+__device__ __forceinline__ void fk_small_train_body(const LayerConst* __restrict__ lcp,
+                                                    const PPConst* __restrict__ pcp, const FkSmallArgs& s, int64_t B,
+                                                    const ChainTrainArgs& a) {
     constexpr int P = GT + 1, W = E * kWave;
     extern __shared__ double2 tl[];
     __shared__ double red[kFsensMaxWaves];
@@ -312,6 +313,24 @@ fk_small_train_kernel(const LayerConst* __restrict__ lcp, const PPConst* __restr
         a.out[1] = reason;
     }
 }
+
+template <int NORM, int GT, bool TAB, int E, bool TEST>
+__global__ void __launch_bounds__((GT + 2) * kWave)
+fk_small_train_kernel(const LayerConst* __restrict__ lcp, const PPConst* __restrict__ pcp, FkSmallArgs s, int64_t B,
+                      ChainTrainArgs a) {
+    fk_small_train_body<NORM, GT, TAB, E, TEST>(lcp, pcp, s, B, a);
+}
+
+// The ensemble entry: workgroup r runs the loop on args[r] (its own p, m, v, Adam scalars, records, accumulator
+// block and status words; the tables are built into each workgroup's own LDS).  The workgroups share nothing they
+// write and never wait for each other.
+template <int NORM, int GT, bool TAB, int E, bool TEST>
+__global__ void __launch_bounds__((GT + 2) * kWave)
+fk_small_train_ens_kernel(const LayerConst* __restrict__ lcp, const PPConst* __restrict__ pcp, FkSmallArgs s,
+                          int64_t B, const ChainTrainArgs* __restrict__ args) {
+    const ChainTrainArgs a = args[blockIdx.x];
+    fk_small_train_body<NORM, GT, TAB, E, TEST>(lcp, pcp, s, B, a);
+}
 }  // namespace
 
 bool fk_small_train_supported(const LayerConst& hlc, const PPConst& hpc, bool tab, int Nx, int64_t B, int wide,
@@ -321,13 +340,15 @@ bool fk_small_train_supported(const LayerConst& hlc, const PPConst& hpc, bool ta
     return !with_test || (tab && fk_small_supported(hlc, hpc, Nx, B) && B <= hlc.G + 2);
 }
 
-hipError_t launch_fk_small_train(const LayerConst& hlc, const PPConst& hpc, bool tab, const LayerConst* lc,
-                                 const PPConst* pc, const FkSmallArgs& s, int64_t B, const ChainTrainArgs& a, int wide,
-                                 hipStream_t st) {
+// args == nullptr: the single-replica kernel on `a`; else the ensemble kernel, one workgroup per struct of the device
+// array args [n_rep] (a: the host copy of any one of them -- they agree in every field read here)
+static hipError_t launch_fk_train(const LayerConst& hlc, const PPConst& hpc, bool tab, const LayerConst* lc,
+                                  const PPConst* pc, const FkSmallArgs& s, int64_t B, const ChainTrainArgs& a,
+                                  const ChainTrainArgs* args, int64_t n_rep, int wide, hipStream_t st) {
     const bool with_test = a.n_save_test > 0 && a.loss_test != nullptr;
     if (!fk_small_train_supported(hlc, hpc, tab, s.Nx, B, wide, with_test) ||
         (tab && (!hpc.enabled || s.ni != hpc.ni || hpc.ni % kPPPerBlock || !pc)) || a.n_iters < 1 || a.n_save < 1 ||
-        a.n_save_test < 0)
+        a.n_save_test < 0 || (args && (n_rep < 1 || n_rep > kTrainMaxReplicas)))
         return hipErrorNotSupported;
     const int threads = (hlc.G + 2) * kWave;
     const bool two = wide == 2 || (int64_t)s.Nx * B > kWave;   // entries per lane (launch_fk_small_fsens's rule)
@@ -335,11 +356,16 @@ hipError_t launch_fk_small_train(const LayerConst& hlc, const PPConst& hpc, bool
     if (lds > 150 * 1024 || (two && !a.rec)) return hipErrorNotSupported;
 #define KAN_FTRAIN3(NORM, GT, TAB, E, TEST)                                                                        \
     do {                                                                                                         \
-        const void* fn = reinterpret_cast<const void*>(&fk_small_train_kernel<NORM, GT, TAB, E, TEST>);          \
+        const void* fn = args ? reinterpret_cast<const void*>(&fk_small_train_ens_kernel<NORM, GT, TAB, E, TEST>) \
+                              : reinterpret_cast<const void*>(&fk_small_train_kernel<NORM, GT, TAB, E, TEST>);   \
         hipError_t e_ = ensure_dynamic_lds(fn, lds);                                                             \
         if (e_ != hipSuccess) return e_;                                                                         \
-        hipLaunchKernelGGL((fk_small_train_kernel<NORM, GT, TAB, E, TEST>), dim3(1), dim3(threads), lds, st, lc, pc, \
-                           s, B, a);                                                                             \
+        if (args)                                                                                                \
+            hipLaunchKernelGGL((fk_small_train_ens_kernel<NORM, GT, TAB, E, TEST>), dim3((unsigned)n_rep),       \
+                               dim3(threads), lds, st, lc, pc, s, B, args);                                      \
+        else                                                                                                     \
+            hipLaunchKernelGGL((fk_small_train_kernel<NORM, GT, TAB, E, TEST>), dim3(1), dim3(threads), lds, st, lc, pc, \
+                               s, B, a);                                                                         \
     } while (0)
 #define KAN_FTRAIN2(NORM, GT, TAB, E)                                                                              \
     do {                                                                                                         \
@@ -365,6 +391,18 @@ hipError_t launch_fk_small_train(const LayerConst& hlc, const PPConst& hpc, bool
 #undef KAN_FTRAIN2
 #undef KAN_FTRAIN3
     return hipGetLastError();
+}
+
+hipError_t launch_fk_small_train(const LayerConst& hlc, const PPConst& hpc, bool tab, const LayerConst* lc,
+                                 const PPConst* pc, const FkSmallArgs& s, int64_t B, const ChainTrainArgs& a, int wide,
+                                 hipStream_t st) {
+    return launch_fk_train(hlc, hpc, tab, lc, pc, s, B, a, nullptr, 1, wide, st);
+}
+
+hipError_t launch_fk_small_train_ensemble(const LayerConst& hlc, const PPConst& hpc, bool tab, const LayerConst* lc,
+                                          const PPConst* pc, const FkSmallArgs& s, int64_t B, const ChainTrainArgs& a,
+                                          const ChainTrainArgs* args, int64_t n_rep, int wide, hipStream_t st) {
+    return args ? launch_fk_train(hlc, hpc, tab, lc, pc, s, B, a, args, n_rep, wide, st) : hipErrorNotSupported;
 }
 
 }  // namespace kan

@@ -20,6 +20,7 @@
 
 #include "kan_buf.hpp"
 #include "kan_device.hpp"
+#include "kan_ensemble.hpp"
 #include "kan_kernels.hpp"
 #include "kanode_internal.hpp"
 
@@ -1683,7 +1684,8 @@ bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch) {
     return h->spec.rhs_kind == KANODE_RHS_CHAIN && kanode_internal_chain_tsit5_ok(h, batch) &&
            kan::chain_train_supported(h->hlc, h->n_layers, h->P, batch, h->esize, h->chain_wide);
 }
-// The handle's training-loop buffer: result words | (the LV loop's dense-output block) | meta at off_meta, grown on
+// The handle's training-loop buffer: result words | (the loop's private block) | meta at off_meta (an ensemble
+// launch: kan_ensemble.hpp's layout, the per-replica blocks and structs before the one meta), grown on
 // demand; meta is uploaded only when it differs from the last call's bytes.
 static kanode_status train_buf_stage(kanode_handle* h, size_t off_meta, const std::vector<char>& meta, hipStream_t st,
                                      char*& base) {
@@ -1703,9 +1705,55 @@ static kanode_status train_buf_stage(kanode_handle* h, size_t off_meta, const st
     }
     return KANODE_OK;
 }
-kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs* a, const std::vector<char>& meta,
-                                          int64_t res[2], void* stream) {
+// The launch of either loop once a's pointers into the single-replica buffer layout (status words at base, the
+// private block at off_rec) are set, or, with ens, the ensemble launch: the buffer is laid out for ens->R replicas
+// (kan_ensemble.hpp), the per-replica structs are formed from *a and uploaded with the meta, and launch(a, args, R)
+// starts one workgroup per struct.  rec_bytes: a replica's private block (0: none).  Synchronises; res [R][2] =
+// iterations done, stop reason of every replica.
+template <class Launch>
+static kanode_status train_launch(kanode_handle* h, const char* what, kan::ChainTrainArgs* a,
+                                  const kan::EnsembleReplicas* ens, size_t rec_bytes, const std::vector<char>& meta,
+                                  int64_t* res, hipStream_t st, Launch&& launch) {
+    const int64_t R = ens ? ens->R : 1;
+    kan::EnsembleLayout L{};
+    if (ens) L = kan::ensemble_layout(R, rec_bytes, sizeof(kan::ChainTrainArgs));
+    else {   // (the single-replica layout: result words | private block | meta)
+        L.off_rec = 64;
+        L.rec_stride = rec_bytes;
+        L.off_args = L.off_meta = L.off_rec + rec_bytes;
+    }
+    char* base = nullptr;
+    if (const kanode_status r = train_buf_stage(h, L.off_meta, meta, st, base); r != KANODE_OK) return r;
+    const double* md = (const double*)(base + L.off_meta);
+    a->saveat = md;
+    a->saveat_test = md + a->n_save;
+    a->stops = md + a->n_save + a->n_save_test;
+    a->joff = (const int32_t*)(a->stops + a->nstops);
+    a->jrows = a->joff + a->nstops + 2;
+    a->rec = rec_bytes ? (double*)(base + L.off_rec) : nullptr;
+    a->out = (int64_t*)base;
+    const kan::ChainTrainArgs* dargs = nullptr;
+    if (ens) {
+        std::vector<kan::ChainTrainArgs> args((size_t)R);
+        kan::ensemble_fill_args(*a, *ens, L, base, args.data());
+        // (the earlier calls synchronised, so nothing on the device still reads the old structs)
+        HIP_TRY(h, hipMemcpy(base + L.off_args, args.data(), args.size() * sizeof(kan::ChainTrainArgs),
+                             hipMemcpyHostToDevice));
+        dargs = (const kan::ChainTrainArgs*)(base + L.off_args);
+    }
+    const hipError_t e = launch(*a, dargs, R);
+    if (e == hipErrorNotSupported)
+        return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (shape or saveat lists not covered "
+                                                                   "by the one-workgroup training kernel)");
+    if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(res, base, (size_t)R * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return KANODE_OK;
+}
+kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs* a, const kan::EnsembleReplicas* ens,
+                                          const std::vector<char>& meta, int64_t* res, void* stream) {
     const hipStream_t st = (hipStream_t)stream;
+    const char* what = ens ? "kanode_train_ensemble_tsit5" : "kanode_train_tsit5";
     // the dense-output capacity of one forward solve: KANODE_OPT_FUSED_SOLVE_CAP, else the most steps whose dense
     // output still fits in LDS next to the rest (at least 64: a smaller block stays in global memory instead)
     int64_t cap = std::min<int64_t>(h->fused_solve_cap, kan::kChainAdjointMaxSteps);
@@ -1723,28 +1771,18 @@ kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs*
         cap = std::max<int64_t>(kanode_fixed_step_count(a->t0, a->tf, a->dt, kan::kChainAdjointMaxSteps), 1);
     int stage_rec = 0;
     if (!kan::chain_train_lds(cap, a->n_save, a->n_save_test, &stage_rec))
-        return fail(h, KANODE_ERR_UNSUPPORTED, "kanode_train_tsit5: not supported (saveat lists too long for one workgroup's LDS)");
-    const size_t off_rec = 64;
-    const size_t off_meta = off_rec + sizeof(double) * ((size_t)kan::kChainAdjointMaxSteps * 7 * 2 + 2);
-    char* base = nullptr;
-    if (const kanode_status r = train_buf_stage(h, off_meta, meta, st, base); r != KANODE_OK) return r;
-    const double* md = (const double*)(base + off_meta);
-    a->saveat = md;
-    a->saveat_test = md + a->n_save;
-    a->stops = md + a->n_save + a->n_save_test;
-    a->joff = (const int32_t*)(a->stops + a->nstops);
-    a->jrows = a->joff + a->nstops + 2;
+        return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (saveat lists too long for one workgroup's LDS)");
     a->cap = cap;
     a->stage_rec = stage_rec;
-    a->rec = (double*)(base + off_rec);
-    a->out = (int64_t*)base;
-    const hipError_t e = kan::launch_kd_chain_train(h->hlc, h->n_layers, h->dlc(), h->P, *a, st);
-    if (e == hipErrorNotSupported)
-        return fail(h, KANODE_ERR_UNSUPPORTED, "kanode_train_tsit5: not supported (shape not covered by the training kernel)");
-    if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_train: ") + hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(res, a->out, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return KANODE_OK;
+    // the global dense-output block: the single-replica buffer always holds the largest one; every replica of an
+    // ensemble gets its own, of this launch's capacity, and none where the dense output is staged in LDS
+    const size_t rec_bytes = sizeof(double) * ((size_t)(ens ? cap : kan::kChainAdjointMaxSteps) * 7 * 2 + 2);
+    return train_launch(h, what, a, ens, ens && stage_rec ? 0 : rec_bytes, meta, res, st,
+                        [&](const kan::ChainTrainArgs& a0, const kan::ChainTrainArgs* dargs, int64_t R) {
+                            return dargs ? kan::launch_kd_chain_train_ensemble(h->hlc, h->n_layers, h->dlc(), h->P, a0,
+                                                                               dargs, R, st)
+                                         : kan::launch_kd_chain_train(h->hlc, h->n_layers, h->dlc(), h->P, a0, st);
+                        });
 }
 bool kanode_internal_pair_persist_ok(const kanode_handle* h) {
     return h->pair_persist && h->spec.dtype == KANODE_F64 && h->spec.rhs_kind == KANODE_RHS_CHAIN && surrogate_pair(h);
@@ -1811,27 +1849,23 @@ bool kanode_internal_fk_train_ok(const kanode_handle* h, int64_t batch, bool wit
                                          h->fsens_wide, with_test);
 }
 kanode_status kanode_internal_fk_train(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
-                                       const std::vector<char>& meta, int64_t res[2], void* stream) {
+                                       const kan::EnsembleReplicas* ens, const std::vector<char>& meta, int64_t* res,
+                                       void* stream) {
     const hipStream_t st = (hipStream_t)stream;
-    const size_t off_acc = 64;   // the accumulators of the two-entries-per-lane kernel (ChainTrainArgs::rec)
-    const size_t off_meta = off_acc + sizeof(double) * (size_t)kan::kFsensMaxWaves * 2 * 64;
-    char* base = nullptr;
-    if (const kanode_status r = train_buf_stage(h, off_meta, meta, st, base); r != KANODE_OK) return r;
-    const double* md = (const double*)(base + off_meta);
-    a->saveat = md;
-    a->saveat_test = md + a->n_save;
-    a->rec = (double*)(base + off_acc);
-    a->out = (int64_t*)base;
+    const char* what = ens ? "kanode_train_forward_ensemble_tsit5" : "kanode_train_forward_tsit5";
+    // the accumulators of the two-entries-per-lane kernel (ChainTrainArgs::rec; launch_fk_small_fsens's rule): every
+    // replica of an ensemble has its own block, and none where the kernel keeps them in LDS
+    const bool two = h->fsens_wide == 2 || h->spec.nx * batch > 64;
+    const size_t rec_bytes = sizeof(double) * (size_t)kan::kFsensMaxWaves * 2 * 64;
     const bool tab = h->pp_on && h->hpc.enabled;
-    const hipError_t e = kan::launch_fk_small_train(h->hlc[0], h->hpc, tab, h->dlc(), h->dpc(), fk_small_args(h), batch, *a,
-                                                    h->fsens_wide, st);
-    if (e == hipErrorNotSupported)
-        return fail(h, KANODE_ERR_UNSUPPORTED, "kanode_train_forward_tsit5: not supported (shape or saveat lists not "
-                                               "covered by the one-workgroup training kernel)");
-    if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_fk_small_train: ") + hipGetErrorString(e));
-    HIP_TRY(h, hipMemcpyAsync(res, a->out, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(h, hipStreamSynchronize(st));
-    return KANODE_OK;
+    return train_launch(h, what, a, ens, ens && !two ? 0 : rec_bytes, meta, res, st,
+                        [&](const kan::ChainTrainArgs& a0, const kan::ChainTrainArgs* dargs, int64_t R) {
+                            return dargs ? kan::launch_fk_small_train_ensemble(h->hlc[0], h->hpc, tab, h->dlc(), h->dpc(),
+                                                                               fk_small_args(h), batch, a0, dargs, R,
+                                                                               h->fsens_wide, st)
+                                         : kan::launch_fk_small_train(h->hlc[0], h->hpc, tab, h->dlc(), h->dpc(),
+                                                                      fk_small_args(h), batch, a0, h->fsens_wide, st);
+                        });
 }
 kanode_status kanode_internal_fk_fsens(kanode_handle* h, const void* p, const void* u0, int64_t batch,
                                        const kan::ChainSolveArgs* a, void* s_save, void* stream) {

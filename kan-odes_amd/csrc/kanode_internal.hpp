@@ -17,6 +17,7 @@ namespace kan {
 struct ChainSolveArgs;
 struct ChainAdjointArgs;
 struct ChainTrainArgs;
+struct EnsembleReplicas;
 struct AdjStepArgs;
 struct PairAdjArgs;
 struct FkLoopArgs;
@@ -129,10 +130,12 @@ kanode_status kanode_internal_chain_adjoint(kanode_handle* h, const void* p, int
 // at this batch, and one launch.  meta = saveat [n_save] | saveat_test [n_save_test] | stops [nstops] (doubles),
 // then joff [nstops + 2] | jrows (int32): kept on the handle (uploaded only when it differs from the last call's),
 // as are the dense-output block and the two result words; a's pointers to them, cap and stage_rec are set here.
-// Synchronises; res = iterations done, stop reason.
+// Synchronises; res = iterations done, stop reason.  With ens (kan_ensemble.hpp: kanode_train_ensemble_tsit5) the
+// launch runs ens->R replicas, one workgroup each: the buffer then holds every replica's result words and
+// dense-output block, the per-replica argument structs formed from *a, and ONE copy of meta; res is [R][2].
 bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch);
-kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs* a, const std::vector<char>& meta,
-                                          int64_t res[2], void* stream);
+kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs* a, const kan::EnsembleReplicas* ens,
+                                          const std::vector<char>& meta, int64_t* res, void* stream);
 // the persistent surrogate-pair adjoint (kd_pair_adjoint_kernel): whether the handle takes it
 // (KANODE_OPT_PAIR_PERSIST, fp64 surrogate pair), its workgroup count, and the launch (launched =
 // false when the kernel does not cover the shape / batch)
@@ -157,10 +160,11 @@ kanode_status kanode_internal_fk_fsens(kanode_handle* h, const void* p, const vo
 // kanode_train_forward_tsit5): whether the handle takes it at this batch (with_test: with the logged-loss solve),
 // and one launch.  meta = saveat [n_save] | saveat_test [n_save_test] (doubles), kept on the handle with the two
 // result words as kanode_internal_chain_train keeps its own; a's pointers to them are set here.  Synchronises;
-// res = iterations done, stop reason.
+// res = iterations done, stop reason; ens as for kanode_internal_chain_train (kanode_train_forward_ensemble_tsit5).
 bool kanode_internal_fk_train_ok(const kanode_handle* h, int64_t batch, bool with_test);
 kanode_status kanode_internal_fk_train(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
-                                       const std::vector<char>& meta, int64_t res[2], void* stream);
+                                       const kan::EnsembleReplicas* ens, const std::vector<char>& meta, int64_t* res,
+                                       void* stream);
 void kanode_internal_clear_adjoint_steps(kanode_handle* h);
 std::vector<double>* kanode_internal_adjoint_steps(kanode_handle* h);
 kanode_status kanode_internal_pair_adjoint(kanode_handle* h, const void* p, int64_t batch, kan::PairAdjArgs* a,

@@ -1,6 +1,7 @@
 // kanode_train.cpp — the entry points that run whole problems in one launch around the solver's storage
 // (include/kanode.h): forward sensitivities of a small Fisher-KPP field (kanode_forward_sensitivity_tsit5) and
 // the two device-resident training loops (kanode_train_tsit5, kanode_train_forward_tsit5).
+#include "kan_ensemble.hpp"
 #include "kanode_solve_internal.hpp"
 
 extern "C" int64_t kanode_forward_sensitivity_step_sizes(kanode_handle* h, double* ts, double* dts, int64_t cap) {
@@ -80,7 +81,10 @@ extern "C" int32_t kanode_train_supported(const kanode_handle* h, int64_t batch)
 
 // The two device-resident loops share everything but the kernel: `forward` = the Fisher-KPP loop on the forward-mode
 // gradient (kanode_train_forward_tsit5), else the Lotka-Volterra loop on the InterpolatingAdjoint (kanode_train_tsit5).
-static kanode_status train_tsit5_impl(bool forward, kanode_handle* h, void* p, void* m, void* v, const void* u0, int64_t batch,
+// ens: the ensemble entries' per-replica arrays (p, m, v and the outputs are then [R][..], iters_done and stop_reason
+// [R]; eta, beta1_t, beta2_t and the handle's L1 penalty are not read), else null.
+static kanode_status train_tsit5_impl(bool forward, const kan::EnsembleReplicas* ens, kanode_handle* h, void* p, void* m,
+                                            void* v, const void* u0, int64_t batch,
                                             double t0, double tf, const double* saveat, int64_t n_save,
                                             const void* target, double tf_test, const double* saveat_test,
                                             int64_t n_save_test, const void* target_test,
@@ -89,35 +93,54 @@ static kanode_status train_tsit5_impl(bool forward, kanode_handle* h, void* p, v
                                             double* loss_test, void* grad, void* p_before, int64_t* counts,
                                             int64_t* iters_done, int32_t* stop_reason, void* stream) {
     SOLVE_TRY(kanode_internal_check(h));
-    if (iters_done) *iters_done = 0;
-    if (stop_reason) *stop_reason = KANODE_TRAIN_OK;
+    const std::string name = std::string(forward ? "kanode_train_forward" : "kanode_train") + (ens ? "_ensemble_tsit5" : "_tsit5");
+    if (ens && (ens->R < 1 || ens->R > kan::kTrainMaxReplicas))
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": 1 <= n_replicas <= 4096");
+    const int64_t R = ens ? ens->R : 1;
+    for (int64_t r = 0; r < R; ++r) {
+        if (iters_done) iters_done[r] = 0;
+        if (stop_reason) stop_reason[r] = KANODE_TRAIN_OK;
+    }
     const kanode_solver_options o = resolved(opt);
     SOLVE_TRY(check_opts(h, o));
-    const std::string name = forward ? "kanode_train_forward_tsit5" : "kanode_train_tsit5";
     if (!forward && (batch < 1 || !kanode_internal_chain_train_ok(h, batch)))
         return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
-                                    "kanode_train_tsit5: not supported (covered: one trajectory of an fp64 chain [2,10,2], "
+                                    name + ": not supported (covered: one trajectory of an fp64 chain [2,10,2], "
                                     "G = 5, rbf, base activations, tanh_fast / softsign, fused_solve and chain_wide on)");
     if (forward && (batch < 1 || !kanode_internal_fk_train_ok(h, batch, false)))
         return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
-                                    "kanode_train_forward_tsit5: not supported (covered: the shapes of "
+                                    name + ": not supported (covered: the shapes of "
                                     "kanode_forward_sensitivity_tsit5)");
-    if (forward && kanode_get_l1_penalty(h) != 0.0)
+    if (forward && !ens && kanode_get_l1_penalty(h) != 0.0)
         return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
                                     "kanode_train_forward_tsit5: not supported (the L1 penalty of "
                                     "kanode_set_l1_penalty is kanode_train_tsit5's alone; set it to 0)");
+    if (ens && ens->l1)
+        for (int64_t r = 0; r < R; ++r) {
+            if (forward && ens->l1[r] != 0.0)
+                return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
+                                            name + ": not supported (the Fisher-KPP loop has no L1 term: l1 must be "
+                                            "NULL or all zero)");
+            if (!(ens->l1[r] >= 0.0 && ens->l1[r] <= 1.7976931348623157e308))
+                return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": l1 must be finite and >= 0");
+        }
     if (forward && n_save_test > 0 && !kanode_internal_fk_train_ok(h, batch, true))
         return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
-                                    "kanode_train_forward_tsit5: not supported (the test problem needs the one-workgroup "
+                                    name + ": not supported (the test problem needs the one-workgroup "
                                     "plain solve: even nx <= 64, the table path and fused_solve on, batch <= G + 2)");
+    if (ens && (!ens->eta || !ens->beta_t))
+        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": eta and beta_t are host arrays of n_replicas entries");
     if (!p || !m || !v || !u0 || !target || !loss || !saveat || n_save < 1 || n_iters < 1 || !(tf > t0) || !iters_done ||
         !stop_reason)
         return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": null pointer, n_save < 1, n_iters < 1 or tf <= t0");
     if (n_save_test < 0 || (n_save_test > 0 && (!saveat_test || !target_test || !loss_test || !(tf_test > t0))))
         return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": test problem needs saveat_test, target_test, loss_test and tf_test > t0");
     // 1 - β^t must stay positive: the bias corrections divide by it (kanode_adam_step's condition)
-    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && beta1_t < 1.0 && beta2_t < 1.0))
-        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": Adam needs 0 <= beta < 1 and beta_t < 1");
+    for (int64_t r = 0; r < R; ++r) {
+        const double b1t = ens ? ens->beta_t[2 * r] : beta1_t, b2t = ens ? ens->beta_t[2 * r + 1] : beta2_t;
+        if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && b1t < 1.0 && b2t < 1.0))
+            return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": Adam needs 0 <= beta < 1 and beta_t < 1");
+    }
     if (check_saveat(saveat, n_save, tf, &t0) != kSaveatOk || check_saveat(saveat_test, n_save_test, tf_test, &t0) != kSaveatOk)
         return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": saveat must ascend within [t0, tf]");
     hipStream_t st = (hipStream_t)stream;
@@ -168,19 +191,27 @@ static kanode_status train_tsit5_impl(bool forward, kanode_handle* h, void* p, v
     a.grad = (double*)grad;
     a.p_before = (double*)p_before;
     a.counts = counts;
-    a.act_reg = forward ? 0.0 : kanode_get_l1_penalty(h);
-    int64_t res[2] = {0, 0};
-    if (forward) SOLVE_TRY(kanode_internal_fk_train(h, batch, &a, meta, res, st));
-    else SOLVE_TRY(kanode_internal_chain_train(h, &a, meta, res, st));
-    *iters_done = res[0];
-    *stop_reason = (int32_t)res[1];
-    if (res[1] != KANODE_TRAIN_OK) {
-        static const char* const why[] = {"", "forward Tsit5: maxiters reached", "forward dense-output capacity exceeded "
-                                          "(KANODE_OPT_FUSED_SOLVE_CAP)", "adjoint Tsit5: maxiters reached",
-                                          "loss is not finite", "test-loss Tsit5: maxiters reached"};
-        const int64_t r = res[1] >= 1 && res[1] <= 5 ? res[1] : 0;
-        return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": stopped at iteration " +
-                                                                   std::to_string(res[0]) + ": " + why[r]);
+    a.act_reg = forward || ens ? 0.0 : kanode_get_l1_penalty(h);   // (an ensemble's: per replica, from ens->l1)
+    std::vector<int64_t> res(2 * (size_t)R, 0);
+    if (forward) SOLVE_TRY(kanode_internal_fk_train(h, batch, &a, ens, meta, res.data(), st));
+    else SOLVE_TRY(kanode_internal_chain_train(h, &a, ens, meta, res.data(), st));
+    static const char* const why[] = {"", "forward Tsit5: maxiters reached", "forward dense-output capacity exceeded "
+                                      "(KANODE_OPT_FUSED_SOLVE_CAP)", "adjoint Tsit5: maxiters reached",
+                                      "loss is not finite", "test-loss Tsit5: maxiters reached"};
+    int64_t bad = -1;   // the lowest replica that stopped
+    for (int64_t r = R - 1; r >= 0; --r) {
+        iters_done[r] = res[2 * r];
+        stop_reason[r] = (int32_t)res[2 * r + 1];
+        if (res[2 * r + 1] != KANODE_TRAIN_OK) bad = r;
+    }
+    if (bad >= 0) {
+        const int64_t code = res[2 * bad + 1], w = code >= 1 && code <= 5 ? code : 0;
+        const kanode_status st_ = kanode_internal_fail(h, KANODE_ERR_INVALID_ARG,
+                                                       name + (ens ? ": replica " + std::to_string(bad) : std::string()) +
+                                                           ": stopped at iteration " + std::to_string(res[2 * bad]) +
+                                                           ": " + why[w]);
+        // (an ensemble launch that ran is a success: the per-replica arrays say who stopped, the text names the first)
+        return ens ? KANODE_OK : st_;
     }
     return KANODE_OK;
 }
@@ -193,7 +224,7 @@ extern "C" kanode_status kanode_train_tsit5(kanode_handle* h, void* p, void* m, 
                                             double eps, double beta1_t, double beta2_t, int64_t n_iters, double* loss,
                                             double* loss_test, void* grad, void* p_before, int64_t* counts,
                                             int64_t* iters_done, int32_t* stop_reason, void* stream) {
-    return train_tsit5_impl(false, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+    return train_tsit5_impl(false, nullptr, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
                             n_save_test, target_test, opt, eta, beta1, beta2, eps, beta1_t, beta2_t, n_iters, loss,
                             loss_test, grad, p_before, counts, iters_done, stop_reason, stream);
 }
@@ -212,7 +243,61 @@ extern "C" kanode_status kanode_train_forward_tsit5(kanode_handle* h, void* p, v
                                                     double beta2_t, int64_t n_iters, double* loss, double* loss_test,
                                                     void* grad, void* p_before, int64_t* counts, int64_t* iters_done,
                                                     int32_t* stop_reason, void* stream) {
-    return train_tsit5_impl(true, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+    return train_tsit5_impl(true, nullptr, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
                             n_save_test, target_test, opt, eta, beta1, beta2, eps, beta1_t, beta2_t, n_iters, loss,
                             loss_test, grad, p_before, counts, iters_done, stop_reason, stream);
+}
+
+// ---- the ensemble entries: n_replicas independent loops in one launch, one workgroup each ----
+static kanode_status train_ensemble(bool forward, kanode_handle* h, int64_t n_replicas, void* p, void* m, void* v,
+                                    const void* u0, int64_t batch, double t0, double tf, const double* saveat,
+                                    int64_t n_save, const void* target, double tf_test, const double* saveat_test,
+                                    int64_t n_save_test, const void* target_test, const kanode_solver_options* opt,
+                                    const double* eta, const double* l1, double beta1, double beta2, double eps,
+                                    const double* beta_t, int64_t n_iters, double* loss, double* loss_test, void* grad,
+                                    void* p_before, int64_t* counts, int64_t* iters_done, int32_t* stop_reason,
+                                    void* stream) {
+    kan::EnsembleReplicas e{};
+    e.R = n_replicas;
+    e.P = h ? kanode_internal_param_length(h) : 0;
+    e.n_iters = n_iters;
+    e.p = (double*)p;
+    e.m = (double*)m;
+    e.v = (double*)v;
+    e.eta = eta;
+    e.l1 = l1;
+    e.beta_t = beta_t;
+    e.loss = loss;
+    e.loss_test = loss_test;
+    e.grad = (double*)grad;
+    e.p_before = (double*)p_before;
+    e.counts = counts;
+    return train_tsit5_impl(forward, &e, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+                            n_save_test, target_test, opt, 0.0, beta1, beta2, eps, 0.0, 0.0, n_iters, loss, loss_test,
+                            grad, p_before, counts, iters_done, stop_reason, stream);
+}
+
+extern "C" kanode_status kanode_train_ensemble_tsit5(kanode_handle* h, int64_t n_replicas, void* p, void* m, void* v,
+                                                     const void* u0, int64_t batch, double t0, double tf,
+                                                     const double* saveat, int64_t n_save, const void* target,
+                                                     double tf_test, const double* saveat_test, int64_t n_save_test,
+                                                     const void* target_test, const kanode_solver_options* opt,
+                                                     const double* eta, const double* l1, double beta1, double beta2,
+                                                     double eps, const double* beta_t, int64_t n_iters, double* loss,
+                                                     double* loss_test, void* grad, void* p_before, int64_t* counts,
+                                                     int64_t* iters_done, int32_t* stop_reason, void* stream) {
+    return train_ensemble(false, h, n_replicas, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+                          n_save_test, target_test, opt, eta, l1, beta1, beta2, eps, beta_t, n_iters, loss, loss_test,
+                          grad, p_before, counts, iters_done, stop_reason, stream);
+}
+
+extern "C" kanode_status kanode_train_forward_ensemble_tsit5(
+    kanode_handle* h, int64_t n_replicas, void* p, void* m, void* v, const void* u0, int64_t batch, double t0, double tf,
+    const double* saveat, int64_t n_save, const void* target, double tf_test, const double* saveat_test,
+    int64_t n_save_test, const void* target_test, const kanode_solver_options* opt, const double* eta, const double* l1,
+    double beta1, double beta2, double eps, const double* beta_t, int64_t n_iters, double* loss, double* loss_test,
+    void* grad, void* p_before, int64_t* counts, int64_t* iters_done, int32_t* stop_reason, void* stream) {
+    return train_ensemble(true, h, n_replicas, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+                          n_save_test, target_test, opt, eta, l1, beta1, beta2, eps, beta_t, n_iters, loss, loss_test,
+                          grad, p_before, counts, iters_done, stop_reason, stream);
 }

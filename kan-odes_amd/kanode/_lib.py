@@ -112,6 +112,11 @@ OPTIONS = {"pointwise_table": OPT_POINTWISE_TABLE, "fused_step": OPT_FUSED_STEP,
            "chain_wide": OPT_CHAIN_WIDE, "record_adjoint_steps": OPT_RECORD_ADJOINT_STEPS,
            "fk_device_loop": OPT_FK_DEVICE_LOOP, "fsens_wide": OPT_FSENS_WIDE}
 
+_ENSEMBLE_ARGS = [_H, C.c_int64, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int64,
+                  _P, C.c_double, C.POINTER(C.c_double), C.c_int64, _P, C.POINTER(SolverOptsC),
+                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double,
+                  C.POINTER(C.c_double), C.c_int64, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P]
+
 SIGNATURES = [
     ("kanode_create", C.c_int, [C.POINTER(SpecC), C.POINTER(C.c_void_p)]),
     ("kanode_destroy", None, [_H]),
@@ -167,6 +172,8 @@ SIGNATURES = [
                                              C.c_int64, _P, C.POINTER(SolverOptsC), C.c_double, C.c_double, C.c_double,
                                              C.c_double, C.c_double, C.c_double, C.c_int64, _P, _P, _P, _P, _P,
                                              C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P]),
+    ("kanode_train_ensemble_tsit5", C.c_int, _ENSEMBLE_ARGS),
+    ("kanode_train_forward_ensemble_tsit5", C.c_int, _ENSEMBLE_ARGS),
     ("kanode_comm_unique_id", C.c_int, [_P]),
     ("kanode_comm_create", C.c_int, [C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(_P)]),
     ("kanode_comm_allreduce_sum", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),

@@ -458,6 +458,65 @@ class KanodeHandle:
         return dict(loss=loss, loss_test=loss_t, grad=grad, p_before=pb, counts=counts, iters_done=int(done.value),
                     stop=L.TRAIN_STOP.get(int(stop.value), str(stop.value)), error=err)
 
+    def train_ensemble_tsit5(self, p, m, v, u0, t0: float, tf: float, saveat, target, opts: "L.SolverOptsC", eta,
+                             beta, eps: float, beta_t, n_iters: int, test=None, record: bool = False, l1=None):
+        """train_tsit5 on R independent replicas in one launch, one workgroup each (kanode_train_ensemble_tsit5):
+        p, m, v are [R, P] and updated in place, eta and l1 (None: all zero) sequences of R floats, beta_t R pairs
+        of running powers.  Returns train_tsit5's dict with a leading replica dimension on loss, loss_test, grad,
+        p_before and counts; iters_done and stop are lists of R; error is the library's text naming the lowest
+        stopped replica, or None.  A replica that stops does not raise and does not hold up the others."""
+        return self._train_ensemble("kanode_train_ensemble_tsit5", p, m, v, u0, t0, tf, saveat, target, opts, eta, l1,
+                                    beta, eps, beta_t, n_iters, test, record)
+
+    def train_forward_ensemble_tsit5(self, p, m, v, u0, t0: float, tf: float, saveat, target, opts: "L.SolverOptsC",
+                                     eta, beta, eps: float, beta_t, n_iters: int, test=None, record: bool = False,
+                                     l1=None):
+        """train_ensemble_tsit5 for a small Fisher-KPP field (kanode_train_forward_ensemble_tsit5); a non-zero
+        entry of l1 raises "not supported"."""
+        return self._train_ensemble("kanode_train_forward_ensemble_tsit5", p, m, v, u0, t0, tf, saveat, target, opts,
+                                    eta, l1, beta, eps, beta_t, n_iters, test, record)
+
+    def _train_ensemble(self, name, p, m, v, u0, t0, tf, saveat, target, opts, eta, l1, beta, eps, beta_t, n_iters,
+                        test, record):
+        B = u0.shape[0] if u0.dim() == 2 else 1
+        if p.dim() != 2 or p.shape[0] < 1:
+            raise ValueError("train_ensemble_tsit5 needs p, m, v of shape [R, P]")
+        R = int(p.shape[0])
+        for t, nm in ((p, "p"), (m, "m"), (v, "v")):
+            self._check_t(t, (R, self.P), nm)
+        self._check_t(u0, None, "u0")
+        if u0.numel() != B * self.N:
+            raise ValueError("train_ensemble_tsit5 needs u0 of B x N entries")
+        self._check_t(target, (len(saveat),) + tuple(u0.shape), "target")
+        eta = [float(e) for e in eta]
+        bt = [float(x) for pair in beta_t for x in pair]
+        if len(eta) != R or len(bt) != 2 * R or (l1 is not None and len(l1) != R):
+            raise ValueError("train_ensemble_tsit5 needs R entries of eta, l1 and beta_t")
+        c_eta = (C.c_double * R)(*eta)
+        c_bt = (C.c_double * (2 * R))(*bt)
+        c_l1 = None if l1 is None else (C.c_double * R)(*[float(x) for x in l1])
+        n = int(n_iters)
+        kw = dict(dtype=torch.float64, device=self.device)
+        loss = torch.zeros((R, n), **kw)
+        tf_t, sv_t, n_t, tg_t, loss_t = 0.0, None, 0, None, None
+        if test is not None:
+            tf_t, sat, tg_t = test
+            self._check_t(tg_t, (len(sat),) + tuple(u0.shape), "target_test")
+            sv_t, n_t = self._saveat_c(sat), len(sat)
+            loss_t = torch.zeros((R, n), **kw)
+        grad = torch.zeros((R, n, self.P), **kw) if record else None
+        pb = torch.zeros((R, n, self.P), **kw) if record else None
+        counts = torch.zeros((R, n, 4), dtype=torch.int64, device=self.device) if record else None
+        done, stop = (C.c_int64 * R)(), (C.c_int32 * R)()
+        L.check(getattr(L.lib(), name)(self._h, R, _ptr(p), _ptr(m), _ptr(v), _ptr(u0), B, float(t0), float(tf),
+                                       self._saveat_c(saveat), len(saveat), _ptr(target), float(tf_t), sv_t, n_t,
+                                       _ptr(tg_t), C.byref(opts), c_eta, c_l1, float(beta[0]), float(beta[1]),
+                                       float(eps), c_bt, n, _ptr(loss), _ptr(loss_t), _ptr(grad), _ptr(pb),
+                                       _ptr(counts), done, stop, _stream(self.device)), self._h, name)
+        err = L.lib().kanode_last_error(self._h).decode() if any(s != 0 for s in stop) else None
+        return dict(loss=loss, loss_test=loss_t, grad=grad, p_before=pb, counts=counts, iters_done=list(done),
+                    stop=[L.TRAIN_STOP.get(int(s), str(s)) for s in stop], error=err)
+
     def table_rejections(self):
         """Intervals the last table builds rejected: (φ, φ', swish), -1 for a table not built yet
         (kanode_table_rejections; their points take the direct formula)."""

@@ -7,6 +7,7 @@
                   mean folded in; what Trainer uses on the GPU
     mse_loss    — `mean(abs2, X .- pred)` (LV_driver_KANODE.jl:197-203, Fisher-KPP_Source.jl:107-109)
     reg_loss    — L1 + entropy on the flat p (LV_driver_KANODE.jl:187-194)
+    EnsembleTrainer — R independent Trainers of one problem; on the GPU all of them in one launch per chunk
     Trainer     — one iteration = forward Tsit5 solve, loss, the gradient by the
                   InterpolatingAdjoint (the reference's NeuralODE default sensealg; native
                   kanode_adjoint_tsit5 on the GPU) wherever the RHS provides the adjoint stage,
@@ -392,3 +393,206 @@ class Trainer:
         if record:
             out["grad"], out["p_before"], out["counts"] = cat("grad", False), cat("p_before", False), cat("counts", True)
         return out
+
+
+class EnsembleTrainer:
+    """R independent trainings of one problem side by side: seeds, learning rates or penalty weights.
+
+    p0 is [R, P]; eta and sparse_reg are a float or a sequence of R.  Where the handle covers the problem (the
+    conditions of Trainer.run's device loops, evaluated once for the shared problem) run() takes all live replicas
+    through ONE launch per chunk, one workgroup each (kanode_train_ensemble_tsit5 /
+    kanode_train_forward_ensemble_tsit5), and replica r computes bit for bit what Trainer computes from the same
+    state.  Everything else is the host path: R Trainers stepped in turn, on the CPU too.
+
+    State: p, m, v ([R, P]; row r is replica r's, and its Trainer's optimiser works on these rows in place), bp (R
+    pairs of running powers), history (R lists), stopped ({r: (iterations the replica had done, reason)})."""
+
+    def __init__(self, rhs, u0, tspan, saveat, target, p0, eta=5e-4, solver: Tsit5Options | None = None,
+                 sparse_reg=0.0, sensealg: str | None = None):
+        if not isinstance(p0, torch.Tensor) or p0.dim() != 2 or p0.shape[0] < 1:
+            raise ValueError("EnsembleTrainer: p0 must be a tensor of shape [R, P]")
+        R = int(p0.shape[0])
+
+        def per_replica(x, name):
+            xs = [float(x)] * R if isinstance(x, (int, float)) else [float(e) for e in x]
+            if len(xs) != R:
+                raise ValueError(f"EnsembleTrainer: {name} must be a float or a sequence of R = {R} floats")
+            return xs
+        self.R = R
+        self.eta, self.sparse_reg = per_replica(eta, "eta"), per_replica(sparse_reg, "sparse_reg")
+        self.rhs, self.u0, self.tspan, self.saveat, self.target = rhs, u0, tspan, saveat, target
+        self.solver = solver or Tsit5Options()
+        self.p = p0.detach().clone().contiguous()
+        self.m, self.v = torch.zeros_like(self.p), torch.zeros_like(self.p)
+        self._members = []
+        for r in range(R):        # replica r's Trainer works on row r of p, m, v in place
+            tr = Trainer(rhs, u0, tspan, saveat, target, self.p[r], eta=self.eta[r], solver=self.solver,
+                         sparse_reg=self.sparse_reg[r], sensealg=sensealg)
+            tr.p = self.p[r]
+            tr.opt.state[id(tr.p)] = [self.m[r], self.v[r], list(tr.opt.beta)]
+            self._members.append(tr)
+        self.sensealg = self._members[0].sensealg
+        self.stopped = {}
+        self.last_run = None      # "device_adjoint", "device_forward" or "host"
+
+    @property
+    def bp(self):
+        return [tr.opt.state[id(tr.p)][2] for tr in self._members]
+
+    @property
+    def history(self):
+        return [tr.history for tr in self._members]
+
+    def live(self):
+        return [r for r in range(self.R) if r not in self.stopped]
+
+    def member(self, r: int) -> Trainer:
+        """A Trainer on clones of replica r's p, m, v, running powers and history: to continue one member alone,
+        prune it or checkpoint it.  The ensemble is not changed by what happens to it."""
+        src = self._members[r]
+        tr = Trainer(self.rhs, self.u0, self.tspan, self.saveat, self.target, self.p[r], eta=self.eta[r],
+                     solver=self.solver, sparse_reg=self.sparse_reg[r], sensealg=src.sensealg)
+        tr.opt.state[id(tr.p)] = [self.m[r].clone(), self.v[r].clone(), list(self.bp[r])]
+        tr.history = list(src.history)
+        tr._pver = src._pver
+        return tr
+
+    def best(self):
+        """(r, loss): the live replica with the smallest last recorded loss."""
+        cand = [(tr.history[-1], r) for r, tr in enumerate(self._members) if r not in self.stopped and tr.history]
+        if not cand:
+            raise ValueError("EnsembleTrainer.best: no live replica has a recorded loss")
+        loss, r = min(cand)
+        return r, loss
+
+    def default_chunk(self, n_live: int) -> int:
+        """The largest chunk with ceil(n_live / CUs) * chunk <= 256 (at least 1): workgroups beyond one per compute
+        unit run in waves, and one launch stays as long as Trainer.run's 256-iteration launch."""
+        if not self.p.is_cuda:
+            return 256
+        cus = torch.cuda.get_device_properties(self.p.device).multi_processor_count
+        return max(1, 256 // -(-n_live // max(1, cus)))
+
+    def _device_path(self, with_test: bool):
+        probe = next((tr for tr in self._members if tr.sparse_reg), self._members[0])
+        return probe._native_run_path(with_test)          # (a penalty on any replica sends a Fisher-KPP field to the host)
+
+    def run(self, n_iters: int, test=None, chunk: int | None = None, record: bool = False) -> dict:
+        """n_iters iterations of every live replica.  Returns Trainer.run's dict with a leading replica dimension
+        (loss, loss_test [R, n_iters]; with record grad, p_before [R, n_iters, P] and counts [R, n_iters, 4]) plus
+        iters_done (R ints, this run's) and stop (R reason names, "ok" for a replica that ran through).
+
+        A replica that stops (a solve at maxiters, the dense-output capacity, a non-finite loss) does not raise:
+        it keeps the p, m, v of its last good iteration, its later entries of loss are NaN (its records zero), it
+        enters self.stopped and later runs leave it out.  run raises only when every replica has stopped."""
+        from . import _lib as L
+        n_iters = int(n_iters)
+        if n_iters < 0 or (chunk is not None and chunk < 1):
+            raise ValueError("run: n_iters >= 0 and chunk >= 1")
+        if not self.live():
+            raise L.KanodeError(f"EnsembleTrainer.run: every replica has stopped: {self.stopped}")
+        R, P = self.R, self.p.shape[1]
+        nan = float("nan")
+        out = {"loss": torch.full((R, n_iters), nan, dtype=torch.float64),
+               "loss_test": torch.full((R, n_iters), nan, dtype=torch.float64) if test is not None else None}
+        if record:
+            out["grad"], out["p_before"] = self.p.new_zeros((R, n_iters, P)), self.p.new_zeros((R, n_iters, P))
+            out["counts"] = torch.zeros((R, n_iters, 4), dtype=torch.int64)
+        done, stop = [0] * R, ["ok"] * R
+        dev, tst = None, None
+        if test is not None:
+            tspan_t, saveat_t, target_t = test
+            sv_t = _saveat_list(tspan_t, saveat_t)
+            sv_t = [s for s in sv_t if s <= float(tspan_t[1]) + 1e-12 * max(1.0, abs(float(tspan_t[1])))]
+        if n_iters > 0:
+            dev = self._device_path(test is not None)
+            if dev is not None and test is not None:
+                if float(tspan_t[0]) == float(self.tspan[0]) and tuple(target_t.shape) == (len(sv_t),) + tuple(self.u0.shape):
+                    tst = (float(tspan_t[1]), sv_t, target_t.contiguous())
+                else:
+                    dev = None
+        self.last_run = dev or "host"
+        if dev is None:
+            self._run_host(n_iters, test, record, out, done, stop)
+        else:
+            self._run_native(n_iters, tst, chunk, record, dev == "device_forward", out, done, stop)
+        out["iters_done"], out["stop"] = done, stop
+        if not self.live():
+            raise L.KanodeError(f"EnsembleTrainer.run: every replica has stopped: {self.stopped}")
+        return out
+
+    def _stop(self, r, reason, stop):
+        self.stopped[r] = (len(self._members[r].history), reason)
+        stop[r] = reason
+
+    def _run_host(self, n_iters, test, record, out, done, stop):
+        import math
+        for r in self.live():
+            tr = self._members[r]
+            for it in range(n_iters):
+                st = tr.opt.state[id(tr.p)]
+                keep = (tr.p.clone(), st[0].clone(), st[1].clone(), list(st[2]))
+                o = tr.run(1, test=test, record=record)
+                if not math.isfinite(float(o["loss"][0])):   # the device loops' rule: stop before the update
+                    tr.p.copy_(keep[0])
+                    st[0].copy_(keep[1])
+                    st[1].copy_(keep[2])
+                    st[2][:] = keep[3]
+                    tr.history.pop()
+                    tr._pver -= 1
+                    self._stop(r, "loss_not_finite", stop)
+                    break
+                for key in ("loss", "loss_test") + (("grad", "p_before", "counts") if record else ()):
+                    if o[key] is not None:
+                        out[key][r, it] = o[key][0]
+                done[r] = it + 1
+
+    def _run_native(self, n_iters, test, chunk, record, forward, out, done, stop):
+        hd = self.rhs.hd
+        sv, _ = self._members[0]._fast_path()
+        b1, b2 = self._members[0].opt.beta
+        oc = self.solver.to_c()
+        target = self.target.contiguous()
+        call = hd.train_forward_ensemble_tsit5 if forward else hd.train_ensemble_tsit5
+        bps = self.bp
+        keys = ("loss", "loss_test") + (("grad", "p_before", "counts") if record else ())
+        at = 0
+        while at < n_iters and self.live():
+            live = self.live()
+            k = min(n_iters - at, int(chunk) if chunk is not None else self.default_chunk(len(live)))
+            # a stopped replica is left out of the launch: the live rows are gathered, and scattered back after it
+            whole = len(live) == self.R
+            idx = torch.as_tensor(live, device=self.p.device)
+            p, m, v = (self.p, self.m, self.v) if whole else (x[idx].contiguous() for x in (self.p, self.m, self.v))
+            res = call(p, m, v, self.u0, float(self.tspan[0]), float(self.tspan[1]), sv, target, oc,
+                       [self.eta[r] for r in live], (b1, b2), self._members[0].opt.eps, [bps[r] for r in live], k,
+                       test=test, record=record, l1=None if forward else [self.sparse_reg[r] for r in live])
+            if not whole:
+                for dst, src in ((self.p, p), (self.m, m), (self.v, v)):
+                    dst[idx] = src
+            host = {key: (res[key].cpu() if key in ("loss", "loss_test", "counts") and res[key] is not None
+                          else res[key]) for key in keys}
+            ran_through = all(d == k for d in res["iters_done"])
+            if ran_through:                                   # (the usual case: whole blocks at once)
+                for key in keys:
+                    if host[key] is not None:
+                        rows = idx.to(out[key].device)
+                        out[key][rows, at:at + k] = host[key]
+            losses = host["loss"].tolist()
+            for j, r in enumerate(live):
+                tr, d = self._members[r], int(res["iters_done"][j])
+                bp = bps[r]
+                for _ in range(d):                            # Flux's βp .*= β, once per iteration done
+                    bp[0] *= b1
+                    bp[1] *= b2
+                tr._pver += d
+                tr._drop_pre()
+                tr.history.extend(losses[j][:d])
+                if not ran_through:
+                    for key in keys:
+                        if host[key] is not None:
+                            out[key][r, at:at + d] = host[key][j, :d]
+                done[r] += d
+                if res["stop"][j] != "ok":
+                    self._stop(r, res["stop"][j], stop)
+            at += k
