@@ -34,8 +34,12 @@ def cfgs_from_specs(specs):
 
 
 def chain_scale(specs, p, u):
-    """Per-output Σ|terms|: the chain evaluated with |C|, |W| and every basis value >= 0
-    bounds the rounding-error scale of y (rbf/rswaf/iqf values are positive)."""
+    """Per-output Σ|terms| proxy: the chain evaluated with |C|, |W| and every basis value >= 0
+    (rbf/rswaf/iqf values are positive).  A proxy, not a bound: it has no term for the rounding of the
+    basis argument (amplified by invh = (G-1)/2) and, pushed through a pullback, it keeps the signs of
+    the basis derivatives.  It holds on the shapes it is used on (softsign/tanh_fast rbf chains with
+    G <= 10 and the golden fixtures); at G = 32 the fp32 oracle itself leaves it, and it is 0 for an
+    identity layer off the grid.  The first-order bound is layer_cases.error_scale."""
     ap = np.abs(p)
     y = O.chain_fwd(specs, ap, u)
     return np.abs(y) + np.max(np.abs(y)) * 1e-3
