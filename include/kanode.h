@@ -214,6 +214,15 @@ kanode_status kanode_reserve(kanode_handle* h, int64_t max_batch);
  *     entries still take the one-entry kernel.  2 (tests) = the two-entry kernel for every nx·batch <= 128:
  *     with an empty upper half it returns the one-entry kernel's bits.  Any other value is INVALID_ARG.
  *     kanode_forward_sensitivity_supported follows the option.
+ *   KANODE_OPT_TRAIN_ANY_CHAIN (default 0): which shapes kanode_train_tsit5 covers.  0 = one Lotka-Volterra
+ *     trajectory (the shape listed at kanode_train_tsit5).  1 = also every other fp64 chain whose forward solve
+ *     and adjoint each run in one workgroup (every layer <= 16 wide, up to 4 layers, batch <= 16, one normalizer /
+ *     basis path for all layers, KANODE_OPT_FUSED_SOLVE on): a pruned [2 -> k -> 2], a [3 -> 6 -> 3] chain, three
+ *     layers, a batch of trajectories.  Those run kd_chain_train_wg_kernel: the forward and adjoint device
+ *     functions of the two-launch path, the loss summed on one wave (so a loss differs from the host loop's
+ *     torch-summed one in the last bits, which is why the coverage is opt-in).  The Lotka-Volterra shape runs its
+ *     own kernel whatever the option says, with the same bits.  kanode_train_supported follows the option; the
+ *     ensemble entry does not (it stays the Lotka-Volterra shape's).  Any value other than 0 / 1 is INVALID_ARG.
  * Options are read when a call is issued (never from the environment).  kanode_get_option
  * returns the current value, or -1 for an unknown option. */
 typedef enum {
@@ -236,7 +245,8 @@ typedef enum {
     KANODE_OPT_CHAIN_WIDE = 17,
     KANODE_OPT_RECORD_ADJOINT_STEPS = 18,
     KANODE_OPT_FK_DEVICE_LOOP = 19,
-    KANODE_OPT_FSENS_WIDE = 20
+    KANODE_OPT_FSENS_WIDE = 20,
+    KANODE_OPT_TRAIN_ANY_CHAIN = 21
 } kanode_option;
 typedef enum {
     KANODE_ADJ_NONE = 0,            /* no adjoint on this handle yet */
@@ -428,8 +438,9 @@ kanode_status kanode_adam_step(void* x, void* m, void* v, const void* g, int64_t
  *
  * Covered (kanode_train_supported): an fp64 chain [2 -> 10 -> 2], G = 5, rbf basis, base activation on both
  * layers, tanh_fast or softsign, batch = 1, with KANODE_OPT_FUSED_SOLVE and KANODE_OPT_CHAIN_WIDE on -- the shapes
- * whose adjoint is the stage-parallel one-workgroup kernel.  Anything else: KANODE_ERR_UNSUPPORTED, nothing
- * launched.  opt->control is ignored.
+ * whose adjoint is the stage-parallel one-workgroup kernel.  With KANODE_OPT_TRAIN_ANY_CHAIN = 1 also the other
+ * small fp64 chains listed at that option, at batch <= 16: u0 is then [batch][N] and the targets [n_save][batch][N].
+ * Anything else: KANODE_ERR_UNSUPPORTED, nothing launched.  opt->control is ignored.
  *
  * Ownership: p, m, v ([P], device) are the caller's and are updated in place; u0 ([2]), target ([n_save][2]) and
  * target_test ([n_save_test][2]) are device arrays the call only reads; saveat and saveat_test are host arrays
@@ -537,8 +548,9 @@ kanode_status kanode_train_forward_tsit5(kanode_handle* h, void* p, void* m, voi
  * why, and the other replicas run on.  The call synchronises the stream and returns KANODE_OK whenever the launch
  * ran, even if some replica stopped; kanode_last_error then names the lowest stopped replica.
  *
- * Covered: exactly the shapes of kanode_train_supported / kanode_train_forward_supported.  Anything else:
- * KANODE_ERR_UNSUPPORTED, nothing launched.  A capturing stream is refused (KANODE_ERR_CAPTURE). */
+ * Covered: exactly the shapes of kanode_train_supported / kanode_train_forward_supported, the former with
+ * KANODE_OPT_TRAIN_ANY_CHAIN at 0 whatever the handle's value (replicas of a general chain are out of scope).
+ * Anything else: KANODE_ERR_UNSUPPORTED, nothing launched.  A capturing stream is refused (KANODE_ERR_CAPTURE). */
 kanode_status kanode_train_ensemble_tsit5(kanode_handle* h, int64_t n_replicas, void* p, void* m, void* v,
                                           const void* u0, int64_t batch, double t0, double tf, const double* saveat,
                                           int64_t n_save, const void* target, double tf_test,

@@ -443,20 +443,28 @@ train_supported(h::Handle, B::Integer) = ccall(sym(:kanode_train_supported), Int
 # λ of kanode_train_tsit5's L1 term (finite, >= 0; 0 = plain MSE).  kanode_train_forward_tsit5 refuses a non-zero one.
 set_l1_penalty!(h::Handle, λ::Real) = check(h, ccall(sym(:kanode_set_l1_penalty), Cint, (Ptr{Cvoid}, Float64), h.ptr, λ))
 l1_penalty(h::Handle) = ccall(sym(:kanode_get_l1_penalty), Float64, (Ptr{Cvoid},), h.ptr)
+# KANODE_OPT_TRAIN_ANY_CHAIN (include/kanode.h): 1 = train_tsit5! also covers every other small fp64 chain whose solve
+# and adjoint each run in one workgroup (a pruned [2,k,2], a [3,6,3] chain, three layers, up to 16 trajectories)
+const OPT_TRAIN_ANY_CHAIN = Int32(21)
+train_any_chain!(h::Handle, v::Integer = 1) = check(h, ccall(sym(:kanode_set_option), Cint, (Ptr{Cvoid}, Int32, Int64),
+                                                             h.ptr, OPT_TRAIN_ANY_CHAIN, v))
 
 """train_tsit5!(h, p, m, v, u0, tspan, saveat, target, n_iters, loss; η, β, ϵ, βp, test, loss_test, grad, p_before,
 counts, opt) -> (iters_done, stop_reason).  loss[it] is the loss at p_it (before the update), loss_test[it] at
 p_{it+1}; test = (tf_test, saveat_test, target_test).  A stopped loop (stop_reason != 0: a kanode_train_stop)
 returns normally with p, m, v as the last good iteration left them; any other failure throws.
 l1: the weight λ of the sparsity term of sparse_on = 1 (LV_driver_KANODE.jl:187-201: loss + λ·Σ|p|, gradient +
-λ·sign(p)), set on the handle for this call and restored afterwards."""
+λ·sign(p)), set on the handle for this call and restored afterwards.
+Covered by default: one Lotka-Volterra trajectory (B = 1).  After train_any_chain!(h) (KANODE_OPT_TRAIN_ANY_CHAIN = 1)
+also the other small fp64 chains, e.g. a pruned network, at B <= 16 trajectories: u0 is then N x B and target
+N x B x n_save (column-major; the C side's [n_save][B][N])."""
 function train_tsit5!(h::Handle, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cvoid}, u0::Ptr{Cvoid}, tspan,
                       saveat::Vector{Float64}, target::Ptr{Cvoid}, n_iters::Integer, loss::Ptr{Cvoid};
                       η::Real = 1e-3, β = (0.9, 0.999), ϵ::Real = 1e-8, βp = β, test = nothing,
                       loss_test::Ptr{Cvoid} = C_NULL, grad::Ptr{Cvoid} = C_NULL, p_before::Ptr{Cvoid} = C_NULL,
                       counts::Ptr{Cvoid} = C_NULL, opt::SolverOptions = default_options(),
-                      stream::Ptr{Cvoid} = C_NULL, l1::Real = 0.0)
-    train_supported(h, 1) || throw(ArgumentError("train_tsit5!: not covered for this handle"))
+                      stream::Ptr{Cvoid} = C_NULL, l1::Real = 0.0, B::Integer = 1)
+    train_supported(h, B) || throw(ArgumentError("train_tsit5!: not covered for this handle (train_any_chain!?)"))
     issorted(saveat) || throw(ArgumentError("saveat must be ascending"))
     tf_t, sv_t, tg_t = test === nothing ? (0.0, Float64[], Ptr{Cvoid}(C_NULL)) : (Float64(test[1]), Vector{Float64}(test[2]), test[3])
     done = Ref{Int64}(0)
@@ -470,7 +478,7 @@ function train_tsit5!(h::Handle, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cvoid}, u0
              Ptr{Cvoid}, Float64, Ptr{Float64}, Int64, Ptr{Cvoid}, Ref{SolverOptions}, Float64, Float64, Float64,
              Float64, Float64, Float64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Int64},
              Ref{Int32}, Ptr{Cvoid}),
-            h.ptr, p, m, v, u0, 1, tspan[1], tspan[2], saveat, length(saveat), target, tf_t, sv_t, length(sv_t), tg_t,
+            h.ptr, p, m, v, u0, B, tspan[1], tspan[2], saveat, length(saveat), target, tf_t, sv_t, length(sv_t), tg_t,
             opt, η, β[1], β[2], ϵ, βp[1], βp[2], n_iters, loss, loss_test, grad, p_before, counts, done, stop, stream)
     finally
         set_l1_penalty!(h, old)

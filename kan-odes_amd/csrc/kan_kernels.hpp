@@ -506,6 +506,12 @@ struct ChainTrainArgs {
     int64_t* out;                  // iters_done, ChainTrainStop
     double act_reg;                // λ of the L1 term λ·Σ|p| in the loss (kd_chain_train_lvsp_kernel; 0: plain MSE).
                                    // The Fisher-KPP loop has no such term and ignores it.
+    // kd_chain_train_wg_kernel alone (launch_kd_chain_train_wg sets them; zero elsewhere): B trajectories of N
+    // entries (u0 [B·N], target [n_save][B·N]); rec is then [cap][7][B·N] | k1_0 [B·N] | u_save / dl [n_save][B·N] |
+    // the test u_save [n_save_test][B·N] (the last two used when !dl_lds), stage_rec: the adjoint copies the dense
+    // output into LDS first (the WideModel adjoint, where launch_kd_chain_adjoint stages it)
+    int64_t B, N;
+    int32_t dl_lds, pad;
 };
 bool chain_train_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B, size_t esize, bool wide);
 // the dynamic LDS of a launch with these sizes, and whether the dense output of `cap` steps is staged in it;
@@ -513,6 +519,20 @@ bool chain_train_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B,
 size_t chain_train_lds(int64_t cap, int64_t n_save, int64_t n_save_test, int* stage_rec);
 hipError_t launch_kd_chain_train(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P,
                                  const ChainTrainArgs& a, hipStream_t st);
+// The same loop for every other small chain the one-workgroup forward and adjoint cover (kd_chain_train_wg_kernel,
+// kan_train_wg.hip; KANODE_OPT_TRAIN_ANY_CHAIN): fp64, B <= kChainSolveMaxBatch trajectories, the forward by
+// onewg_tsit5 on ChainModel, the adjoint by onewg_adjoint on the model launch_kd_chain_adjoint picks (WideModel for
+// one trajectory of a two-layer chain that passes wide_fits, else ChainModel).  Not the LV-wave shape
+// (chain_train_supported: kd_chain_train_lvsp_kernel keeps it).
+bool chain_train_wg_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B, size_t esize, bool wide);
+// the dynamic LDS of a launch with these sizes (0: does not fit the 140 KB budget); *dl_lds: u_save / dl and the
+// test u_save live in LDS (else in rec), *stage_rec: the adjoint stages the dense output in LDS
+size_t chain_train_wg_lds(const LayerConst* hlcs, int nl, int64_t P, int64_t B, bool wide, int64_t cap, int64_t n_save,
+                          int64_t n_save_test, int* dl_lds, int* stage_rec);
+// doubles of ChainTrainArgs::rec for these sizes
+size_t chain_train_wg_rec_elems(int64_t n, int64_t cap, int64_t n_save, int64_t n_save_test);
+hipError_t launch_kd_chain_train_wg(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P, int64_t B,
+                                    bool wide, const ChainTrainArgs& a, hipStream_t st);
 // The ensemble entries of both loops: n_rep independent replicas in one launch, workgroup r on args[r] (a device
 // array; `a` is the host copy of any one struct: the replicas differ only in p, m, v, eta, act_reg, bp1 / bp2, rec,
 // out and the record pointers).  No workgroup reads another's data or waits for it.

@@ -1,0 +1,467 @@
+// kan_train_wg.hip — K whole training iterations of a small chain in ONE launch (gfx950), for every shape the
+// one-workgroup forward and adjoint cover that kan_train.hip's Lotka-Volterra kernel does not: a pruned [2,k,2],
+// a [3,6,3] chain, three layers, up to kChainSolveMaxBatch trajectories (KANODE_OPT_TRAIN_ANY_CHAIN).
+//
+// The loop is LV_driver_KANODE.jl:279-291, as in kan_train.hip; here every phase runs on the whole workgroup, with
+// the device functions of the two-launch path (kan_onewg.hpp on the model classes of kan_col.hip).  Per iteration it:
+//   A  wg_forward: onewg_tsit5 in block mode on ChainModel (kd_chain_tsit5_kernel's arithmetic) at p_it; the dense
+//      output [step][u_n, k_2..k_7][N·B] and k1_0 go to global memory (ChainTrainArgs::rec), ts / dts stay in LDS.
+//      barrier.  wg_loss (wave 0): loss[it] = wave_mse (+ l1_loss with a penalty), u_save <- dl = (u - X)·2/numel.
+//      With a test problem and it > 0: wg_forward again over (t0, tf_test) at the same p_it, barrier, wg_test_loss
+//      -> loss_test[it - 1] (the last one after the loop).
+//   -- barrier; every thread reads the status words and takes the same stop decision
+//   B  wg_adjoint: onewg_adjoint on the model launch_kd_chain_adjoint picks: WideModel (one trajectory of a
+//      two-layer chain that passes wide_fits; block of kChainBlock) or ChainModel (block of ⌈16 B / 64⌉ waves), with
+//      that launcher's LDS carve (rows or the Wide scratch, μ [2][P], kμ [7][P]); WideModel copies the dense output
+//      into LDS first where it fits in that launcher's 60 KB.  The gradient μ goes to LDS.
+//   -- barrier
+//   C  wg_adam: the records (counts, grad, p_before), the gradient μ (+ λ·sgn(p)), adam_entry per parameter
+//      spread over the block -> p (global and the LDS copy), m, v
+//   -- barrier; βp1, βp2 advance by one rounded product in every thread
+// The forward runs in the adjoint's block: at B = 1 under WideModel that is four waves where kd_chain_tsit5_kernel
+// has one; onewg_bsum then adds the idle waves' zeros, which changes no bit of a sum of squares.
+// The global dense output is written in A and read in B by the same workgroup; the barrier between them (a
+// workgroup-scope release / acquire, with the stores waited for) orders them, as for kan_train_body.inc's global
+// record.  Each phase is a function of its own (not inlined): a phase's registers are then not live across the
+// others (DESIGN §7 on the 368 B/lane of scratch of the one-body LV kernel).
+#define KAN_COL_DEVICE_ONLY
+#include "kan_col.hip"
+#include "kan_train_loss.hpp"
+
+namespace kan {
+
+enum TrainWgModel : int { kWgNone = 0, kWgChain = 1, kWgWide = 2 };
+
+// LDS of a launch, in doubles after the layer constants: ps [P] | work (ChainModel: rows [NG][P]; WideModel: its
+// scratch) | μ [2][P] | kμ [7][P] | the gradient [P] | ts, dts [cap] each | saveat [n_save] | the test saveat
+// [n_save_test] | (dl_lds) u_save / dl [n_save][n], the test u_save [n_save_test][n] | (stage_rec) the dense output
+// [(7 cap + 1) n].  work, μ and kμ are contiguous (zeroed together, as the adjoint kernels do).
+struct TrainWgCarve {
+    size_t ps, work, mu, km, gl, tsl, dtsl, sv, svt, dl, ust, recl, total;   // doubles, from the end of the constants
+};
+__host__ __device__ inline TrainWgCarve train_wg_carve(int64_t P, int64_t work, int64_t cap, int64_t n_save,
+                                                       int64_t n_save_test, int64_t n, int dl_lds, int stage_rec) {
+    TrainWgCarve c{};
+    size_t o = 0;
+    c.ps = o, o += P;
+    c.work = o, o += work;
+    c.mu = o, o += 2 * P;
+    c.km = o, o += 7 * P;
+    c.gl = o, o += P;
+    c.tsl = o, o += cap;
+    c.dtsl = o, o += cap;
+    c.sv = o, o += n_save;
+    c.svt = o, o += n_save_test;
+    c.dl = o, o += dl_lds ? n_save * n : 0;
+    c.ust = o, o += dl_lds ? n_save_test * n : 0;
+    c.recl = o, o += stage_rec ? (cap * 7 + 1) * n : 0;
+    c.total = o;
+    return c;
+}
+
+// what every phase needs besides the launch's arguments: pointers into LDS, typed as such (a phase is a function of
+// its own, and through a plain pointer argument it would read LDS with flat loads), and the global dense-output block
+#define KAN_LDS __attribute__((address_space(3)))
+struct TrainWgPtrs {
+    KAN_LDS const double* tab;       // the exp table
+    KAN_LDS const LayerConst* lcl;
+    KAN_LDS double *ps, *work, *mu, *km, *gl, *tsl, *dtsl, *sv, *svt, *recl;
+    double *dl, *ust;        // u_save / dl and the test u_save: LDS (dl_lds) or global
+    double *rec, *rk1;       // global: [cap][7][n], k1_0 [n]
+    KAN_LDS double* red;     // onewg_bsum's partials
+    KAN_LDS int64_t* fo;     // [3][4]: the counters of the training forward, the test solve, the adjoint
+    KAN_LDS double* lossv;   // loss[it]
+    int nl, P;
+};
+
+// A value every lane holds alike, moved to scalar registers.  The phases read their arguments from private memory
+// (structs passed by reference to functions that are not inlined), where the compiler cannot know that they are
+// wave-uniform: without this every solver option is a vector register and every step-control branch a vector branch.
+template <typename T>
+__device__ __forceinline__ T wg_uniform(T v) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two scalar registers");
+    int x[sizeof(T) / 4];
+    __builtin_memcpy(x, &v, sizeof(T));
+#pragma unroll
+    for (int i = 0; i < (int)(sizeof(T) / 4); ++i) x[i] = __builtin_amdgcn_readfirstlane(x[i]);
+    __builtin_memcpy(&v, x, sizeof(T));
+    return v;
+}
+
+// A: the solve at p_it over (t0, tf), dense output kept, or (tst) the test solve over (t0, tf_test)
+template <int FN, int PATH, class FS>
+__device__ __noinline__ void wg_forward(const ChainTrainArgs& a, const TrainWgPtrs& L, bool tst_) {
+    const bool tst = wg_uniform((int)tst_) != 0;
+    ChainSolveArgs fa{};
+    fa.t0 = wg_uniform(a.t0);
+    fa.tf = wg_uniform(tst ? a.tf_test : a.tf);
+    fa.dt = wg_uniform(a.dt);
+    fa.abstol = wg_uniform(a.abstol);
+    fa.reltol = wg_uniform(a.reltol);
+    fa.dtmin = wg_uniform(a.dtmin);
+    fa.beta1 = wg_uniform(a.beta1);
+    fa.beta2 = wg_uniform(a.beta2);
+    fa.gamma = wg_uniform(a.gamma);
+    fa.qmin = wg_uniform(a.qmin);
+    fa.qmax = wg_uniform(a.qmax);
+    fa.qoldinit = wg_uniform(a.qoldinit);
+    fa.adaptive = wg_uniform(a.adaptive);
+    fa.maxiters = wg_uniform(a.maxiters);
+    fa.n_save = wg_uniform(tst ? a.n_save_test : a.n_save);
+    fa.cap = wg_uniform(a.cap);
+    fa.saveat = (const double*)wg_uniform(tst ? L.svt : L.sv);
+    fa.u_save = wg_uniform(tst ? L.ust : L.dl);
+    fa.rec = wg_uniform(tst ? (double*)nullptr : L.rec);
+    fa.k1_0 = wg_uniform(L.rk1);
+    fa.ts = (double*)wg_uniform(L.tsl);
+    fa.dts = (double*)wg_uniform(L.dtsl);
+    fa.out = (int64_t*)wg_uniform(L.fo) + (tst ? 4 : 0);
+    const Math<double> M{(const double*)wg_uniform(L.tab)};
+    const int N = wg_uniform((int)a.N), nl = wg_uniform(L.nl), P = wg_uniform(L.P);
+    const int64_t B = wg_uniform(a.B);
+    const int j = threadIdx.x & (kChainDim - 1);
+    const int64_t col = threadIdx.x / kChainDim;
+    ChainModel<double, FN, PATH, FS> m{M, (const LayerConst*)wg_uniform(L.lcl), nl, (const double*)wg_uniform(L.ps),
+                                       nullptr, P, j, 0, col < B && j < N, (int64_t)N * col + j, (int64_t)N * B};
+    onewg_tsit5<double>(m, wg_uniform(a.u0), fa, (double*)wg_uniform(L.red));
+}
+
+// A: loss[it] and the cotangent in place of u_save, on wave 0
+__device__ __noinline__ void wg_loss(const ChainTrainArgs& a, const TrainWgPtrs& L, int64_t it) {
+    if (threadIdx.x >= kWave) return;
+    double lv = wave_mse<true>(L.dl, a.target, a.n_save * a.N * a.B, a.dl_scale);
+    if (a.act_reg != 0.0) lv = l1_loss(lv, (const double*)L.ps, L.P, a.act_reg);   // (λ = 0: not one operation more)
+    if (threadIdx.x == 0) {
+        a.loss[it] = lv;
+        *L.lossv = lv;
+    }
+}
+
+// A: loss_test[it - 1] from the test solve just run, on wave 0
+__device__ __noinline__ void wg_test_loss(const ChainTrainArgs& a, const TrainWgPtrs& L, int64_t it) {
+    if (threadIdx.x >= kWave) return;
+    const double lt = wave_mse<false>(L.ust, a.target_test, a.n_save_test * a.N * a.B, 0.0);
+    if (threadIdx.x == 0) a.loss_test[it - 1] = L.fo[7] == 0 ? lt : __longlong_as_double(0x7ff8000000000000LL);
+}
+
+// (the generic shapes are too large for the stage loops to be unrolled, as in kan_col.hip's adjoint kernels)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wpass-failed"
+// B: the InterpolatingAdjoint from the dense output just written; the gradient -> L.gl, the counters -> L.fo[8..]
+// ADJ: kWgChain (ChainModel<FN, PATH, FS>, as kd_chain_adjoint_kernel) or kWgWide (WideModel<WN>, as
+// kd_chain_adjoint_wide_kernel)
+template <int ADJ, int WN, int FN, int PATH, class FS>
+__device__ __noinline__ void wg_adjoint(const ChainTrainArgs& a, const TrainWgPtrs& L) {
+    ChainAdjointArgs aa{};
+    aa.t0 = wg_uniform(a.t0);
+    aa.tf = wg_uniform(a.tf);
+    aa.dt = wg_uniform(a.dt);
+    aa.abstol = wg_uniform(a.abstol);
+    aa.reltol = wg_uniform(a.reltol);
+    aa.dtmin = wg_uniform(a.dtmin);
+    aa.beta1 = wg_uniform(a.beta1);
+    aa.beta2 = wg_uniform(a.beta2);
+    aa.gamma = wg_uniform(a.gamma);
+    aa.qmin = wg_uniform(a.qmin);
+    aa.qmax = wg_uniform(a.qmax);
+    aa.qoldinit = wg_uniform(a.qoldinit);
+    aa.adaptive = wg_uniform(a.adaptive);
+    aa.maxiters = wg_uniform(a.maxiters);
+    aa.rec = wg_uniform(L.rec);
+    aa.k1_0 = wg_uniform(L.rk1);
+    aa.ts = (const double*)wg_uniform(L.tsl);
+    aa.dts = (const double*)wg_uniform(L.dtsl);
+    aa.nsteps = wg_uniform(L.fo[0]);
+    aa.dl_du = wg_uniform(L.dl);
+    aa.stops = wg_uniform(a.stops);
+    aa.nstops = wg_uniform(a.nstops);
+    aa.jrows = wg_uniform(a.jrows);
+    aa.joff = wg_uniform(a.joff);
+    aa.dp = (double*)wg_uniform(L.gl);
+    aa.out = (int64_t*)wg_uniform(L.fo) + 8;
+    const Math<double> M{(const double*)wg_uniform(L.tab)};
+    double* const mu = (double*)wg_uniform(L.mu);
+    double* const km = (double*)wg_uniform(L.km);
+    double* const work = (double*)wg_uniform(L.work);
+    const double* const tsl = (const double*)wg_uniform(L.tsl);
+    const double* const dtsl = (const double*)wg_uniform(L.dtsl);
+    const LayerConst* const lcl = (const LayerConst*)wg_uniform(L.lcl);
+    const double* const ps = (const double*)wg_uniform(L.ps);
+    double* const red = (double*)wg_uniform(L.red);
+    const int64_t B = wg_uniform(a.B);
+    const int nl = wg_uniform(L.nl), stage_rec = wg_uniform(a.stage_rec);
+    const int N = wg_uniform((int)a.N), P = wg_uniform(L.P);
+    if constexpr (ADJ == kWgWide) {
+        for (int i = threadIdx.x; i < WideModel<double, WN>::kEnd + 9 * P; i += blockDim.x) work[i] = 0.0;
+        __syncthreads();
+        double* recl = nullptr;
+        if (stage_rec) {
+            recl = (double*)wg_uniform(L.recl);
+            onewg_stage_rec<double>(recl, aa, N);
+        }
+        WideModel<double, WN> m{M, lcl, ps, work, P, (int)threadIdx.x < N, (int64_t)threadIdx.x, (int64_t)N};
+        onewg_adjoint<double>(m, aa, mu, km, tsl, dtsl, red, recl);
+    } else {
+        const int NG = blockDim.x / kChainDim;
+        const int NGa = B < NG ? (int)B : NG;   // groups holding a trajectory
+        for (int i = threadIdx.x; i < NG * P + 9 * P; i += blockDim.x) work[i] = 0.0;
+        __syncthreads();
+        const int j = threadIdx.x & (kChainDim - 1);
+        const int64_t col = threadIdx.x / kChainDim;
+        ChainModel<double, FN, PATH, FS> m{M, lcl, nl, ps, work, P, j, NGa, col < B && j < N, (int64_t)N * col + j,
+                                           (int64_t)N * B};
+        onewg_adjoint<double>(m, aa, mu, km, tsl, dtsl, red);
+    }
+}
+#pragma clang diagnostic pop
+
+// C: the records and Adam, parameter q on thread q mod blockDim
+__device__ __noinline__ void wg_adam(const ChainTrainArgs& a, const TrainWgPtrs& L, int64_t it, double bp1, double bp2) {
+    const int P = L.P;
+    if (a.counts && threadIdx.x == 0) {
+        a.counts[4 * it] = L.fo[0];
+        a.counts[4 * it + 1] = L.fo[1];
+        a.counts[4 * it + 2] = L.fo[8];
+        a.counts[4 * it + 3] = L.fo[9];
+    }
+    AdamArgs ad;
+    ad.scale = 1.0;
+    ad.beta1 = a.ab1;
+    ad.beta2 = a.ab2;
+    ad.omb1 = a.omb1;
+    ad.omb2 = a.omb2;
+    {   // (contraction off: 1 - βp must not fuse with the product that advanced βp)
+#pragma clang fp contract(off)
+        ad.c1 = 1.0 - bp1;
+        ad.c2 = 1.0 - bp2;
+    }
+    ad.eps = a.eps;
+    ad.eta = a.eta;
+    for (int q = threadIdx.x; q < P; q += blockDim.x) {
+        const double x = L.ps[q];
+        double gq = L.gl[q];
+        // ∂(λ·Σ|p|)/∂p_q = λ·sgn(p_q), sgn(0) = 0: one rounded add (λ = 0: none, a -0.0 stays -0.0)
+        if (a.act_reg != 0.0) gq = __dadd_rn(gq, x > 0.0 ? a.act_reg : (x < 0.0 ? -a.act_reg : 0.0));
+        if (a.grad) a.grad[it * P + q] = gq;
+        if (a.p_before) a.p_before[it * P + q] = x;
+        double mq = a.m[q], vq = a.v[q];
+        const double xn = adam_entry<double>(x, mq, vq, gq, ad);
+        a.m[q] = mq;
+        a.v[q] = vq;
+        a.p[q] = xn;
+        L.ps[q] = xn;
+    }
+}
+
+// FN, PATH, FS: the forward's ChainModel specialisation (launch_kd_chain_tsit5's choice for the handle), which is
+// the ChainModel adjoint's too (launch_kd_chain_adjoint's ladder is the same); ADJ, WN: the adjoint's model
+template <int FN, int PATH, class FS, int ADJ, int WN>
+__global__ void __launch_bounds__(kChainBlock)
+kd_chain_train_wg_kernel(const LayerConst* __restrict__ lcs, int nl, int P, ChainTrainArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char tw_raw[];
+    __shared__ double red[kChainBlock / kWave];
+    __shared__ int64_t fo[12];
+    __shared__ double lossv;
+    const int64_t n = a.N * a.B;
+    const int64_t work = ADJ == kWgWide ? (int64_t)WideModel<double, WN>::kEnd : (int64_t)(blockDim.x / kChainDim) * P;
+    const TrainWgCarve c = train_wg_carve(P, work, a.cap, a.n_save, a.n_save_test, n, a.dl_lds, a.stage_rec);
+    double* const base = reinterpret_cast<double*>(tw_raw + nl * sizeof(LayerConst));
+    TrainWgPtrs L;
+    L.lcl = (KAN_LDS const LayerConst*)reinterpret_cast<const LayerConst*>(tw_raw);
+    L.ps = (KAN_LDS double*)(base + c.ps);
+    L.work = (KAN_LDS double*)(base + c.work);
+    L.mu = (KAN_LDS double*)(base + c.mu);
+    L.km = (KAN_LDS double*)(base + c.km);
+    L.gl = (KAN_LDS double*)(base + c.gl);
+    L.tsl = (KAN_LDS double*)(base + c.tsl);
+    L.dtsl = (KAN_LDS double*)(base + c.dtsl);
+    L.sv = (KAN_LDS double*)(base + c.sv);
+    L.svt = (KAN_LDS double*)(base + c.svt);
+    L.rec = a.rec;
+    L.rk1 = a.rec + a.cap * 7 * n;
+    L.dl = a.dl_lds ? base + c.dl : L.rk1 + n;
+    L.ust = a.dl_lds ? base + c.ust : L.rk1 + n + a.n_save * n;
+    L.recl = (KAN_LDS double*)(base + c.recl);
+    L.red = (KAN_LDS double*)red;
+    L.fo = (KAN_LDS int64_t*)fo;
+    L.lossv = (KAN_LDS double*)&lossv;
+    L.nl = nl;
+    L.P = P;
+    {
+        const int nw = nl * (int)(sizeof(LayerConst) / sizeof(int32_t));
+        const int32_t* src = reinterpret_cast<const int32_t*>(lcs);
+        int32_t* dst = reinterpret_cast<int32_t*>(tw_raw);
+        stage_chain_consts(dst, src, nw, base + c.ps, a.p, P);
+        for (int64_t i = threadIdx.x; i < a.n_save; i += blockDim.x) L.sv[i] = a.saveat[i];
+        for (int64_t i = threadIdx.x; i < a.n_save_test; i += blockDim.x) L.svt[i] = a.saveat_test[i];
+        if (threadIdx.x < 12) fo[threadIdx.x] = 0;
+    }
+    KAN_EXP_TABLE_LDS(tab);   // (its barrier also publishes the constants, ps, the saveat lists and fo)
+    L.tab = (KAN_LDS const double*)tab;
+    const bool has_test = a.n_save_test > 0 && a.loss_test != nullptr;
+    double bp1 = a.bp1, bp2 = a.bp2;
+    int64_t done = 0;
+    int reason = kTrainOk;
+    for (int64_t it = 0; it <= a.n_iters; ++it) {
+        const bool tst = has_test && it > 0;
+        if (it == a.n_iters && !tst) break;
+        // ---- A: the solves at p_it, the loss and its cotangent ----
+        if (it < a.n_iters) {
+            wg_forward<FN, PATH, FS>(a, L, false);
+            __syncthreads();   // u_save, the dense output, ts / dts and the counters, to every wave
+            if (fo[3] == 0) wg_loss(a, L, it);
+        }
+        if (tst) {
+            wg_forward<FN, PATH, FS>(a, L, true);
+            __syncthreads();
+            wg_test_loss(a, L, it);
+        }
+        __syncthreads();
+        if (tst && fo[7] != 0) {
+            reason = kTrainTestMaxiters;
+            break;
+        }
+        if (it == a.n_iters) break;
+        if (fo[3] != 0) {
+            reason = fo[3] == 2 ? kTrainDenseCapacity : kTrainForwardMaxiters;
+            break;
+        }
+        if (!(::fabs(lossv) <= 1.7976931348623157e308)) {
+            reason = kTrainLossNotFinite;
+            break;
+        }
+        // ---- B: the InterpolatingAdjoint from the dense output just written ----
+        wg_adjoint<ADJ, WN, FN, PATH, FS>(a, L);
+        __syncthreads();   // the gradient and the adjoint's counters
+        if (fo[11] != 0) {
+            reason = kTrainAdjointMaxiters;
+            break;
+        }
+        // ---- C: records and Adam ----
+        wg_adam(a, L, it, bp1, bp2);
+        __syncthreads();   // p_{it+1} in LDS; every wave is done with dl, the gradient and the counters
+        {   // the rounded products Python's `bp *= β` forms
+#pragma clang fp contract(off)
+            bp1 = bp1 * a.ab1;
+            bp2 = bp2 * a.ab2;
+        }
+        done = it + 1;
+    }
+    if (threadIdx.x == 0) {
+        a.out[0] = done;
+        a.out[1] = reason;
+    }
+}
+
+// the conditions of launch_kd_chain_tsit5 and of launch_kd_chain_adjoint's two one-workgroup models, with `cap` in
+// place of the step count (what holds at cap holds at every count the loop can reach)
+static bool train_wg_small_layers(const LayerConst* hlcs, int nl) {
+    for (int l = 0; l < nl; ++l) {
+        const LayerConst& h = hlcs[l];
+        if (h.I > kChainDim || h.O > kChainDim || h.path != hlcs[0].path || h.norm != hlcs[0].norm) return false;
+        if (l > 0 && h.I != hlcs[l - 1].O) return false;
+    }
+    return true;
+}
+static int train_wg_model(const LayerConst* hlcs, int nl, int64_t P, int64_t B, bool wide, int64_t cap, int* stage_rec) {
+    if (stage_rec) *stage_rec = 0;
+    if (nl < 1 || nl > kChainMaxLayers || B < 1 || B > kChainSolveMaxBatch || I_ne_O(hlcs, nl) || cap < 1 ||
+        cap > kChainAdjointMaxSteps || !train_wg_small_layers(hlcs, nl) ||
+        nl * sizeof(LayerConst) + (size_t)P * sizeof(double) > 48 * 1024 || (nl * sizeof(LayerConst)) % 8)
+        return kWgNone;
+    if (wide && B == 1 && nl == 2 && hlcs[0].use_base && hlcs[1].use_base && hlcs[0].norm == hlcs[1].norm &&
+        hlcs[1].I == hlcs[0].O && wide_fits(WideShape{hlcs[0].I, hlcs[0].O, hlcs[1].O, hlcs[0].G, hlcs[1].G}) &&
+        (hlcs[0].norm == NORM_TANH_FAST || hlcs[0].norm == NORM_SOFTSIGN)) {
+        const size_t pre = 2 * sizeof(LayerConst) + sizeof(double) * ((size_t)P * 10 + WideModel<double, NORM_SOFTSIGN>::kEnd);
+        const size_t lds = pre + 2 * sizeof(double) * cap;
+        const size_t rec = sizeof(double) * ((size_t)cap * 7 + 1) * hlcs[0].I;
+        if (lds <= 60 * 1024) {
+            if (stage_rec) *stage_rec = lds + rec <= 60 * 1024 ? 1 : 0;
+            return kWgWide;
+        }
+    }
+    const int threads = (int)((B * kChainDim + kWave - 1) / kWave) * kWave;
+    const int NG = threads / kChainDim;
+    const size_t lds = nl * sizeof(LayerConst) + (size_t)P * sizeof(double) * (1 + NG + 9) + 2 * sizeof(double) * cap + 16;
+    return lds <= 60 * 1024 ? kWgChain : kWgNone;
+}
+
+size_t chain_train_wg_rec_elems(int64_t n, int64_t cap, int64_t n_save, int64_t n_save_test) {
+    return (size_t)((cap * 7 + 1) * n + (n_save + n_save_test) * n);
+}
+
+size_t chain_train_wg_lds(const LayerConst* hlcs, int nl, int64_t P, int64_t B, bool wide, int64_t cap, int64_t n_save,
+                          int64_t n_save_test, int* dl_lds, int* stage_rec) {
+    constexpr size_t kBudget = 140 * 1024 - 4096;   // chain_train_lds's, less the kernel's static LDS (the exp table)
+    int sr = 0;
+    const int model = train_wg_model(hlcs, nl, P, B, wide, cap, &sr);
+    if (dl_lds) *dl_lds = 0;
+    if (stage_rec) *stage_rec = 0;
+    if (model == kWgNone || n_save < 0 || n_save_test < 0) return 0;
+    const int64_t n = (int64_t)hlcs[0].I * B;
+    const int threads = model == kWgWide ? kChainBlock : (int)((B * kChainDim + kWave - 1) / kWave) * kWave;
+    const int64_t work = model == kWgWide ? (int64_t)WideModel<double, NORM_SOFTSIGN>::kEnd : (int64_t)(threads / kChainDim) * P;
+    const size_t lc = nl * sizeof(LayerConst);
+    auto bytes = [&](int dl, int st) {
+        return lc + sizeof(double) * train_wg_carve(P, work, cap, n_save, n_save_test, n, dl, st).total;
+    };
+    if (bytes(0, 0) > kBudget) return 0;
+    const int dl = bytes(1, 0) <= kBudget ? 1 : 0;
+    if (sr && bytes(dl, 1) > kBudget) sr = 0;
+    if (dl_lds) *dl_lds = dl;
+    if (stage_rec) *stage_rec = sr;
+    return bytes(dl, sr);
+}
+
+bool chain_train_wg_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B, size_t esize, bool wide) {
+    if (esize != sizeof(double) || nl < 1 || chain_is_lv_wave(hlcs, nl, B, wide)) return false;
+    return chain_train_wg_lds(hlcs, nl, P, B, wide, 1, 1, 0, nullptr, nullptr) != 0;
+}
+
+hipError_t launch_kd_chain_train_wg(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P, int64_t B,
+                                    bool wide, const ChainTrainArgs& a, hipStream_t st) {
+    if (!chain_train_wg_supported(hlcs, nl, P, B, sizeof(double), wide) || a.n_iters < 1 || a.B != B ||
+        a.N != hlcs[0].I || !a.rec)
+        return hipErrorNotSupported;
+    int dl = 0, sr = 0;
+    const size_t lds = chain_train_wg_lds(hlcs, nl, P, B, wide, a.cap, a.n_save, a.n_save_test, &dl, &sr);
+    if (lds == 0 || dl != a.dl_lds || sr != a.stage_rec) return hipErrorNotSupported;
+    const int model = train_wg_model(hlcs, nl, P, B, wide, a.cap, nullptr);
+    const int threads = model == kWgWide ? kChainBlock : (int)((B * kChainDim + kWave - 1) / kWave) * kWave;
+    const LayerConst& h = hlcs[0];
+#define KAN_TWG_GO(FN, PATH, FS, ADJ, WN)                                                                            \
+    do {                                                                                                            \
+        const void* fn = reinterpret_cast<const void*>(&kd_chain_train_wg_kernel<FN, PATH, FS, ADJ, WN>);           \
+        const hipError_t e = ensure_dynamic_lds(fn, lds);                                                           \
+        if (e != hipSuccess) return e;                                                                              \
+        hipLaunchKernelGGL((kd_chain_train_wg_kernel<FN, PATH, FS, ADJ, WN>), dim3(1), dim3(threads), lds, st, lcs, \
+                           nl, (int)P, a);                                                                          \
+    } while (0)
+    // the forward's specialisation is launch_kd_chain_tsit5's ladder; only the combinations a handle reaches exist
+    // (a [2,10,2] G = 5 chain on the exact recurrence under WideModel is the LV-wave shape: not this kernel's)
+    const bool tf = h.norm == NORM_TANH_FAST;
+    if (model == kWgWide) {
+        if (tf && h.path == PATH_REC) KAN_TWG_GO(NORM_TANH_FAST, PATH_REC, ChainShapeAny, kWgWide, NORM_TANH_FAST);
+        else if (tf && h.path == PATH_REC_CORR) KAN_TWG_GO(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny, kWgWide, NORM_TANH_FAST);
+        else if (tf) KAN_TWG_GO(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny, kWgWide, NORM_TANH_FAST);
+        else if (h.path == PATH_REC_CORR) KAN_TWG_GO(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny, kWgWide, NORM_SOFTSIGN);
+        else if (h.path == PATH_REC) KAN_TWG_GO(NORM_RUNTIME, PATH_REC, ChainShapeAny, kWgWide, NORM_SOFTSIGN);
+        else KAN_TWG_GO(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny, kWgWide, NORM_SOFTSIGN);
+    } else if (tf && h.path == PATH_REC && chain_is_lv(hlcs, nl)) {
+        KAN_TWG_GO(NORM_TANH_FAST, PATH_REC, ChainShapeLV, kWgChain, NORM_RUNTIME);
+    } else if (tf && h.path == PATH_REC) {
+        KAN_TWG_GO(NORM_TANH_FAST, PATH_REC, ChainShapeAny, kWgChain, NORM_RUNTIME);
+    } else if (h.path == PATH_REC_CORR) {
+        KAN_TWG_GO(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny, kWgChain, NORM_RUNTIME);
+    } else if (h.path == PATH_REC) {
+        KAN_TWG_GO(NORM_RUNTIME, PATH_REC, ChainShapeAny, kWgChain, NORM_RUNTIME);
+    } else {
+        KAN_TWG_GO(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny, kWgChain, NORM_RUNTIME);
+    }
+#undef KAN_TWG_GO
+    return hipGetLastError();
+}
+
+#undef KAN_LDS
+
+}  // namespace kan

@@ -75,6 +75,7 @@ struct kanode_handle {
     bool record_adj_steps = false;    // KANODE_OPT_RECORD_ADJOINT_STEPS
     bool fk_loop = true;              // KANODE_OPT_FK_DEVICE_LOOP
     int fsens_wide = 0;               // KANODE_OPT_FSENS_WIDE
+    bool train_any_chain = false;     // KANODE_OPT_TRAIN_ANY_CHAIN
     double l1_penalty = 0.0;          // kanode_set_l1_penalty: λ of kanode_train_tsit5's loss term λ·Σ|p|
     std::vector<double> adj_steps;    // the last kanode_adjoint_tsit5's accepted step sizes (when recorded)
     bool adj_fused_finish = false;    // KANODE_OPT_ADJ_FUSED_FINISH (measured even with the finish launch)
@@ -1076,6 +1077,7 @@ kanode_status kanode_set_option(kanode_handle* h, int32_t option, int64_t value)
     case KANODE_OPT_RECORD_ADJOINT_STEPS: return flag(h->record_adj_steps, "RECORD_ADJOINT_STEPS");
     case KANODE_OPT_FK_DEVICE_LOOP: return flag(h->fk_loop, "FK_DEVICE_LOOP");
     case KANODE_OPT_FSENS_WIDE: return count(h->fsens_wide, "FSENS_WIDE", 2);
+    case KANODE_OPT_TRAIN_ANY_CHAIN: return flag(h->train_any_chain, "TRAIN_ANY_CHAIN");
     }
     return fail(h, KANODE_ERR_INVALID_ARG, "unknown option " + std::to_string(option));
 }
@@ -1103,6 +1105,7 @@ int64_t kanode_get_option(const kanode_handle* h, int32_t option) {
     case KANODE_OPT_RECORD_ADJOINT_STEPS: return h->record_adj_steps ? 1 : 0;
     case KANODE_OPT_FK_DEVICE_LOOP: return h->fk_loop ? 1 : 0;
     case KANODE_OPT_FSENS_WIDE: return h->fsens_wide;
+    case KANODE_OPT_TRAIN_ANY_CHAIN: return h->train_any_chain ? 1 : 0;
     }
     return -1;
 }
@@ -1680,9 +1683,19 @@ kanode_status kanode_internal_chain_adjoint(kanode_handle* h, const void* p, int
     launched = true;
     return KANODE_OK;
 }
-bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch) {
+// the Lotka-Volterra loop's shapes (kd_chain_train_lvsp_kernel): whatever KANODE_OPT_TRAIN_ANY_CHAIN says
+static bool chain_train_lv_ok(const kanode_handle* h, int64_t batch) {
     return h->spec.rhs_kind == KANODE_RHS_CHAIN && kanode_internal_chain_tsit5_ok(h, batch) &&
            kan::chain_train_supported(h->hlc, h->n_layers, h->P, batch, h->esize, h->chain_wide);
+}
+// with the option on: every other small fp64 chain (kd_chain_train_wg_kernel)
+static bool chain_train_wg_ok(const kanode_handle* h, int64_t batch) {
+    return h->train_any_chain && h->spec.dtype == KANODE_F64 && h->spec.rhs_kind == KANODE_RHS_CHAIN &&
+           kanode_internal_chain_tsit5_ok(h, batch) &&
+           kan::chain_train_wg_supported(h->hlc, h->n_layers, h->P, batch, h->esize, h->chain_wide);
+}
+bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch) {
+    return chain_train_lv_ok(h, batch) || chain_train_wg_ok(h, batch);
 }
 // The handle's training-loop buffer: result words | (the loop's private block) | meta at off_meta (an ensemble
 // launch: kan_ensemble.hpp's layout, the per-replica blocks and structs before the one meta), grown on
@@ -1750,10 +1763,59 @@ static kanode_status train_launch(kanode_handle* h, const char* what, kan::Chain
     HIP_TRY(h, hipStreamSynchronize(st));
     return KANODE_OK;
 }
-kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs* a, const kan::EnsembleReplicas* ens,
-                                          const std::vector<char>& meta, int64_t* res, void* stream) {
+// kanode_train_tsit5 on a chain that is not the Lotka-Volterra loop's (KANODE_OPT_TRAIN_ANY_CHAIN): the capacity by
+// the same rules (the option, a fixed-step solve's own count, else the most steps that leave u_save / dl in LDS, at
+// least 64, else kChainAdjointMaxSteps or what fits), the private block sized for it
+static kanode_status chain_train_wg(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
+                                    const std::vector<char>& meta, int64_t* res, hipStream_t st) {
+    const char* what = "kanode_train_tsit5";
+    const bool wide = h->chain_wide;
+    auto lds = [&](int64_t cap, int* dl, int* sr) {
+        return kan::chain_train_wg_lds(h->hlc, h->n_layers, h->P, batch, wide, cap, a->n_save, a->n_save_test, dl, sr);
+    };
+    int64_t cap = std::min<int64_t>(h->fused_solve_cap, kan::kChainAdjointMaxSteps);
+    if (cap < 1) {
+        auto largest = [&](bool want_dl) {   // the largest cap that fits (want_dl: with u_save / dl in LDS), 0: none
+            int64_t lo = 0, hi = kan::kChainAdjointMaxSteps;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi + 1) / 2;
+                int dl = 0;
+                if (lds(mid, &dl, nullptr) && (dl || !want_dl)) lo = mid;
+                else hi = mid - 1;
+            }
+            return lo;
+        };
+        cap = largest(true);
+        if (cap < 64) cap = largest(false);
+    }
+    if (!a->adaptive && h->fused_solve_cap < 1)
+        cap = std::max<int64_t>(kanode_fixed_step_count(a->t0, a->tf, a->dt, kan::kChainAdjointMaxSteps), 1);
+    int dl = 0, sr = 0;
+    if (cap < 1 || !lds(cap, &dl, &sr))
+        return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (the problem does not fit one workgroup's LDS)");
+    a->cap = cap;
+    a->stage_rec = sr;
+    a->dl_lds = dl;
+    a->B = batch;
+    a->N = h->n_in;
+    const size_t rec_bytes =
+        sizeof(double) * kan::chain_train_wg_rec_elems(a->N * batch, cap, a->n_save, a->n_save_test);
+    return train_launch(h, what, a, nullptr, (rec_bytes + 63) & ~(size_t)63, meta, res, st,
+                        [&](const kan::ChainTrainArgs& a0, const kan::ChainTrainArgs*, int64_t) {
+                            return kan::launch_kd_chain_train_wg(h->hlc, h->n_layers, h->dlc(), h->P, batch, wide, a0, st);
+                        });
+}
+kanode_status kanode_internal_chain_train(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
+                                          const kan::EnsembleReplicas* ens, const std::vector<char>& meta, int64_t* res,
+                                          void* stream) {
     const hipStream_t st = (hipStream_t)stream;
     const char* what = ens ? "kanode_train_ensemble_tsit5" : "kanode_train_tsit5";
+    if (!chain_train_lv_ok(h, batch)) {
+        if (ens || !chain_train_wg_ok(h, batch))   // (an ensemble of general chains is out of scope: nothing launched)
+            return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (the ensemble entry covers one "
+                                                                       "Lotka-Volterra trajectory per replica)");
+        return chain_train_wg(h, batch, a, meta, res, st);
+    }
     // the dense-output capacity of one forward solve: KANODE_OPT_FUSED_SOLVE_CAP, else the most steps whose dense
     // output still fits in LDS next to the rest (at least 64: a smaller block stays in global memory instead)
     int64_t cap = std::min<int64_t>(h->fused_solve_cap, kan::kChainAdjointMaxSteps);

@@ -134,8 +134,11 @@ kanode_status kanode_internal_chain_adjoint(kanode_handle* h, const void* p, int
 // launch runs ens->R replicas, one workgroup each: the buffer then holds every replica's result words and
 // dense-output block, the per-replica argument structs formed from *a, and ONE copy of meta; res is [R][2].
 bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch);
-kanode_status kanode_internal_chain_train(kanode_handle* h, kan::ChainTrainArgs* a, const kan::EnsembleReplicas* ens,
-                                          const std::vector<char>& meta, int64_t* res, void* stream);
+// (KANODE_OPT_TRAIN_ANY_CHAIN: a chain that is not the Lotka-Volterra loop's runs kd_chain_train_wg_kernel; with ens
+// it is refused, nothing launched)
+kanode_status kanode_internal_chain_train(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
+                                          const kan::EnsembleReplicas* ens, const std::vector<char>& meta, int64_t* res,
+                                          void* stream);
 // the persistent surrogate-pair adjoint (kd_pair_adjoint_kernel): whether the handle takes it
 // (KANODE_OPT_PAIR_PERSIST, fp64 surrogate pair), its workgroup count, and the launch (launched =
 // false when the kernel does not cover the shape / batch)

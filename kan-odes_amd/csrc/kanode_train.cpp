@@ -106,7 +106,8 @@ static kanode_status train_tsit5_impl(bool forward, const kan::EnsembleReplicas*
     if (!forward && (batch < 1 || !kanode_internal_chain_train_ok(h, batch)))
         return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
                                     name + ": not supported (covered: one trajectory of an fp64 chain [2,10,2], "
-                                    "G = 5, rbf, base activations, tanh_fast / softsign, fused_solve and chain_wide on)");
+                                    "G = 5, rbf, base activations, tanh_fast / softsign, fused_solve and chain_wide on; "
+                                    "with KANODE_OPT_TRAIN_ANY_CHAIN every fp64 chain of the one-workgroup solve and adjoint)");
     if (forward && (batch < 1 || !kanode_internal_fk_train_ok(h, batch, false)))
         return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
                                     name + ": not supported (covered: the shapes of "
@@ -194,7 +195,7 @@ static kanode_status train_tsit5_impl(bool forward, const kan::EnsembleReplicas*
     a.act_reg = forward || ens ? 0.0 : kanode_get_l1_penalty(h);   // (an ensemble's: per replica, from ens->l1)
     std::vector<int64_t> res(2 * (size_t)R, 0);
     if (forward) SOLVE_TRY(kanode_internal_fk_train(h, batch, &a, ens, meta, res.data(), st));
-    else SOLVE_TRY(kanode_internal_chain_train(h, &a, ens, meta, res.data(), st));
+    else SOLVE_TRY(kanode_internal_chain_train(h, batch, &a, ens, meta, res.data(), st));
     static const char* const why[] = {"", "forward Tsit5: maxiters reached", "forward dense-output capacity exceeded "
                                       "(KANODE_OPT_FUSED_SOLVE_CAP)", "adjoint Tsit5: maxiters reached",
                                       "loss is not finite", "test-loss Tsit5: maxiters reached"};

@@ -100,6 +100,7 @@ OPT_CHAIN_WIDE = 17
 OPT_RECORD_ADJOINT_STEPS = 18
 OPT_FK_DEVICE_LOOP = 19
 OPT_FSENS_WIDE = 20        # 0 / 1 / 2 (include/kanode.h)
+OPT_TRAIN_ANY_CHAIN = 21   # 0 / 1: kanode_train_tsit5 on every small chain (Trainer(device_loop="any"))
 ADJ_NONE, ADJ_HOST_LOOP, ADJ_CHAIN_WG, ADJ_PAIR_PERSIST, ADJ_PAIR_FALLBACK = 0, 1, 2, 3, 4   # kanode_adjoint_path
 TRAIN_STOP = {0: "ok", 1: "forward_maxiters", 2: "dense_capacity", 3: "adjoint_maxiters", 4: "loss_not_finite",
               5: "test_maxiters"}   # kanode_train_stop
@@ -110,7 +111,8 @@ OPTIONS = {"pointwise_table": OPT_POINTWISE_TABLE, "fused_step": OPT_FUSED_STEP,
            "adj_fused_finish": OPT_ADJ_FUSED_FINISH, "pair_persist_max_wg": OPT_PAIR_PERSIST_MAX_WG,
            "pair_persist_abort": OPT_PAIR_PERSIST_ABORT, "last_adjoint": OPT_LAST_ADJOINT,
            "chain_wide": OPT_CHAIN_WIDE, "record_adjoint_steps": OPT_RECORD_ADJOINT_STEPS,
-           "fk_device_loop": OPT_FK_DEVICE_LOOP, "fsens_wide": OPT_FSENS_WIDE}
+           "fk_device_loop": OPT_FK_DEVICE_LOOP, "fsens_wide": OPT_FSENS_WIDE,
+           "train_any_chain": OPT_TRAIN_ANY_CHAIN}
 
 _ENSEMBLE_ARGS = [_H, C.c_int64, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int64,
                   _P, C.c_double, C.POINTER(C.c_double), C.c_int64, _P, C.POINTER(SolverOptsC),

@@ -166,7 +166,7 @@ class KanodeHandle:
         """kanode_set_option by name (include/kanode.h; the names are _lib.OPTIONS: pointwise_table,
         fused_step, fused_solve, fused_solve_cap, grid_rhs, grid_vjp, grid_adj_step, adj_step_rows, pair_vjp,
         pair_fuse, pair_persist, pair_persist_s, adj_fused_finish, pair_persist_max_wg, pair_persist_abort,
-        fsens_wide; last_adjoint is read-only)."""
+        fsens_wide, train_any_chain; last_adjoint is read-only)."""
         if name not in L.OPTIONS:
             raise KeyError(f"unknown option {name!r}; known: {sorted(L.OPTIONS)}")
         L.check(L.lib().kanode_set_option(self._h, L.OPTIONS[name], int(value)), self._h, "kanode_set_option")
@@ -380,7 +380,9 @@ class KanodeHandle:
         return du0, dp, dict(naccept=st.naccept, nreject=st.nreject, nf=st.nf)
 
     def train_supported(self, batch: int) -> bool:
-        """kanode_train_supported: the device-resident training loop covers this handle at `batch` trajectories."""
+        """kanode_train_supported: the device-resident training loop covers this handle at `batch` trajectories
+        (one Lotka-Volterra trajectory; with the `train_any_chain` option on, every small fp64 chain of the
+        one-workgroup solve and adjoint at up to 16 trajectories)."""
         return bool(L.lib().kanode_train_supported(self._h, int(batch)))
 
     def train_forward_supported(self, batch: int, with_test: bool = False) -> bool:

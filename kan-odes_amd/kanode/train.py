@@ -136,12 +136,22 @@ class Trainer:
     (len(saveat), *u0.shape).  `group` is a torch.distributed process group (or None)."""
 
     def __init__(self, rhs, u0, tspan, saveat, target, p0, eta: float = 5e-4, solver: Tsit5Options | None = None,
-                 sparse_reg: float = 0.0, group=None, sensealg: str | None = None, tp: bool = False):
-        """tp=True: `rhs` is grid-sharded (kanode.tp.GridShardedChainRHS); u0/target/p0 are this rank's
+                 sparse_reg: float = 0.0, group=None, sensealg: str | None = None, tp: bool = False,
+                 device_loop: str = "default"):
+        """device_loop: which shapes run() keeps on the device.  "default": one Lotka-Volterra trajectory (and the
+        Fisher-KPP forward loop).  "any": also every other small fp64 chain whose forward solve and adjoint each run
+        in one workgroup (a pruned [2,k,2], a [3,6,3] chain, three layers, up to 16 trajectories): run() turns the
+        handle's `train_any_chain` option on where it is off.  Its losses are summed on one wave, so they agree with
+        step()'s torch-summed ones to rounding, not bitwise, which is why it is not the default.
+
+        tp=True: `rhs` is grid-sharded (kanode.tp.GridShardedChainRHS); u0/target/p0 are this rank's
         slices, the loss is this shard's part of the global mean, gradients are shard-local.  `group`
         is then the ORTHOGONAL data-parallel group (ranks holding the same parameter slice for other
         trajectories); passing the grid-shard group would sum slices of different parameters, so a
         group sharing any rank with rhs.group other than this one is rejected."""
+        if device_loop not in ("default", "any"):
+            raise ValueError(f"Trainer: device_loop must be 'default' or 'any', not {device_loop!r}")
+        self.device_loop = device_loop
         if tp and group is not None:
             _check_orthogonal(group, getattr(rhs, "group", None))
         self.rhs, self.u0, self.tspan, self.saveat, self.target = rhs, u0, tspan, saveat, target
@@ -286,8 +296,11 @@ class Trainer:
             return None                                   # (host / hipGraph step control, replayed steps: step())
         B = self.u0.shape[0] if self.u0.dim() == 2 else 1
         path = self._fast_path()[1]                       # ("auto" resolved; it turns fsens_wide on where it applies)
-        if path == "interpolating_adjoint" and self.sensealg == "interpolating_adjoint" and hd.train_supported(B):
-            return "device_adjoint"
+        if path == "interpolating_adjoint" and self.sensealg == "interpolating_adjoint":
+            if self.device_loop == "any" and hd.get_option("train_any_chain") == 0:
+                hd.set_option("train_any_chain", 1)       # (idempotent, as "auto" turns fsens_wide on)
+            if hd.train_supported(B):
+                return "device_adjoint"
         if path == "forward" and not self.sparse_reg and hd.train_forward_supported(B, with_test):
             return "device_forward"                       # (no L1 term in the Fisher-KPP loop: step() serves it)
         return None
@@ -300,9 +313,11 @@ class Trainer:
         "p_before" ([n_iters, P], on p's device) and "counts" ([n_iters, 4] int64, CPU: forward naccept, nreject,
         adjoint naccept, nreject).
 
-        Where the handle covers it (one Lotka-Volterra trajectory on the InterpolatingAdjoint, or a small Fisher-KPP
-        field on the forward-mode gradient -- explicitly or through "auto" --; fp64, FusedAdam, no group; sparse_reg adds
-        the L1 term inside the Lotka-Volterra loop and sends a Fisher-KPP field to the host loop)
+        Where the handle covers it (one Lotka-Volterra trajectory on the InterpolatingAdjoint; with
+        Trainer(device_loop="any") every small chain of the one-workgroup solve and adjoint, at up to 16 trajectories;
+        or a small Fisher-KPP field on the forward-mode gradient -- explicitly or through "auto" --; fp64, FusedAdam,
+        no group; sparse_reg adds the L1 term inside the InterpolatingAdjoint loops and sends a Fisher-KPP field to the
+        host loop)
         the iterations run on the device (self.last_run says which loop ran: "device_adjoint", "device_forward" or
         "host"; on the forward loop there is no adjoint, and counts[:, 2:] are the logged-loss solve's naccept and nreject
         when a test problem is given, else zero), at most `chunk` per kernel launch (no single kernel runs for long on a shared
@@ -475,6 +490,10 @@ class EnsembleTrainer:
 
     def _device_path(self, with_test: bool):
         probe = next((tr for tr in self._members if tr.sparse_reg), self._members[0])
+        hd = getattr(self.rhs, "hd", None)
+        if hd is not None and self.p.is_cuda and hd.get_option("train_any_chain"):
+            with hd.options(train_any_chain=0):           # (the ensemble entry is the Lotka-Volterra shape's alone)
+                return probe._native_run_path(with_test)
         return probe._native_run_path(with_test)          # (a penalty on any replica sends a Fisher-KPP field to the host)
 
     def run(self, n_iters: int, test=None, chunk: int | None = None, record: bool = False) -> dict:
