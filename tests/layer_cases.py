@@ -238,8 +238,8 @@ CASES = _cases()
 
 
 def np_layers(specs):
-    return [N.Layer(s.in_dims, s.out_dims, s.grid_len, s.normalizer, s.basis, s.use_base_act, s.grid_lims, None,
-                    s.iqf_reference_quirk) for s in specs]
+    return [N.Layer(s.in_dims, s.out_dims, s.grid_len, s.normalizer, s.basis, s.use_base_act, s.grid_lims,
+                    s.denominator, s.iqf_reference_quirk) for s in specs]
 
 
 # ---- the error scale ------------------------------------------------------------------------------------------
