@@ -569,6 +569,39 @@ kanode_status kanode_train_forward_ensemble_tsit5(kanode_handle* h, int64_t n_re
                                                   double* loss_test, void* grad, void* p_before, int64_t* counts,
                                                   int64_t* iters_done, int32_t* stop_reason, void* stream);
 
+/* --- ensemble solve: one problem at n_replicas parameter vectors in ONE launch -----------------
+ * The forward solve of kanode_solve_tsit5 (control = auto, no dense output) at every row of p [n_replicas][P], one
+ * workgroup per replica: predicted trajectories and held-out losses of a whole trained ensemble, a parameter sweep
+ * or a loss landscape, without n_replicas launches and host waits.  Replica r computes, bit for bit, what
+ * kanode_solve_tsit5 computes on this handle from p + r*P; no replica reads another's data or waits for it.
+ *
+ *     p             device array [n_replicas][P], replica-major, contiguous; read only
+ *     u0            device [N, B], shared by all replicas, as are t0, tf, saveat and the options
+ *     saveat        host, ascending within [t0, tf]; n_save >= 1
+ *     u_save        device [n_replicas][n_save][N*B]
+ *     opt           as kanode_solve_tsit5's, checked by the same statements; control is not read
+ *     stats, stop   host arrays [n_replicas]: the counters, and a kanode_solve_stop
+ * 1 <= n_replicas <= 4096.  The per-replica status words, the device copy of saveat and, for the Fisher-KPP field,
+ * one table of the pointwise function per replica live on the handle and are reused (kanode_reserve does not cover
+ * them: the call may allocate).  Every other path of the handle is left as it was, its own table included.
+ *
+ * A replica that reaches maxiters stops alone: stop[r] = KANODE_SOLVE_MAXITERS, stats[r] holds its counters, and the
+ * rows of its u_save block past the last saveat value it reached are LEFT AS THE CALLER PASSED THEM (fill the array
+ * first to tell them apart).  The call synchronises the stream (it reads the status words) and returns KANODE_OK
+ * whenever the launch ran; kanode_last_error then names the lowest stopped replica.
+ *
+ * Covered (kanode_solve_ensemble_supported): exactly the handles and batches for which kanode_solve_tsit5 with
+ * control = auto runs as one workgroup: chains whose layers are at most 16 wide at batch <= 16, fp64 and fp32, and
+ * the Fisher-KPP field with even nx <= 64 at batch <= 16 on the fp64 table path (G = 5 or 10, softsign or
+ * tanh_fast), KANODE_OPT_FUSED_SOLVE on.  Anything else: KANODE_ERR_UNSUPPORTED, nothing launched and nothing
+ * written.  A capturing stream is refused (KANODE_ERR_CAPTURE). */
+typedef enum { KANODE_SOLVE_OK = 0, KANODE_SOLVE_MAXITERS = 1 } kanode_solve_stop;
+int32_t kanode_solve_ensemble_supported(const kanode_handle* h, int64_t batch);
+kanode_status kanode_solve_ensemble_tsit5(kanode_handle* h, int64_t n_replicas, const void* p, const void* u0,
+                                          int64_t batch, double t0, double tf, const double* saveat, int64_t n_save,
+                                          void* u_save, const kanode_solver_options* opt, kanode_solve_stats* stats,
+                                          int32_t* stop, void* stream);
+
 /* --- the data-parallel gradient all-reduce (one process per GPU) -----------------
  * For hosts without a collective of their own (Julia, C): after kanode_adjoint_tsit5 on each rank's
  * trajectory shard, the flat [dp; L] is SUM all-reduced in place over RCCL (xGMI inside a node), then

@@ -582,6 +582,42 @@ function train_forward_ensemble_tsit5!(h::Handle, R::Integer, p::Ptr{Cvoid}, m::
                                n_iters, loss, η, nothing, β, ϵ, βp, test, loss_test, grad, p_before, counts, opt, stream)
 end
 
+# --- the ensemble solve (kanode_solve_ensemble_tsit5): the forward solve of one problem at R parameter vectors in one
+# launch, one workgroup per replica: what an ensemble trained, a parameter sweep, a loss landscape.
+solve_ensemble_supported(h::Handle, B::Integer) =
+    ccall(sym(:kanode_solve_ensemble_supported), Int32, (Ptr{Cvoid}, Int64), h.ptr, B) == 1
+
+"""solve_ensemble_tsit5(h, u0, tspan, ps, saveat; abstol, reltol, dt, adaptive, ...) -> (sol, stats, stop).
+ps is [P, R]: column r holds replica r's parameters (the C side's replica-major [R][P]).  sol is [N, n_save, R] for a
+vector u0 and [N, B, n_save, R] for a matrix, filled with NaN beforehand; stats a vector of R SolveStats; stop[r] is 0,
+or 1 where replica r reached maxiters (a kanode_solve_stop: it does not throw, and its columns past the last stop it
+reached stay NaN).  Covered: solve_ensemble_supported(h, B), i.e. where solve_tsit5 runs as one workgroup."""
+function solve_ensemble_tsit5(h::Handle, u0::AbstractVecOrMat, tspan, ps::AbstractMatrix, saveat::AbstractVector; kw...)
+    size(ps, 1) == h.P || throw(DimensionMismatch("ps has $(size(ps, 1)) rows, the handle $(h.P) parameters"))
+    checku(h, u0, h.nin, "u0")
+    h.nin == h.nout || throw(ArgumentError("an ODE RHS needs a chain with in_dims == out_dims"))
+    T = h.T
+    R, B = size(ps, 2), size(u0, 2)
+    1 <= R <= 4096 || throw(ArgumentError("solve_ensemble_tsit5: 1 <= R <= 4096 replicas"))
+    ts = Vector{Float64}(saveat)
+    (issorted(ts) && !isempty(ts)) || throw(ArgumentError("saveat must be ascending and not empty"))
+    solve_ensemble_supported(h, B) || throw(ArgumentError("solve_ensemble_tsit5: not covered for this handle / batch"))
+    opt = options(; kw...)
+    pd, ud = upload(tohost(T, ps)), upload(tohost(T, u0))
+    out = fill(T(NaN), h.nin, B, length(ts), R)
+    od = upload(out)
+    stats = Vector{SolveStats}(undef, R)
+    stop = zeros(Int32, R)
+    st = GC.@preserve ts stats stop ccall(sym(:kanode_solve_ensemble_tsit5), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float64}, Int64, Ptr{Cvoid},
+         Ref{SolverOptions}, Ptr{SolveStats}, Ptr{Int32}, Ptr{Cvoid}),
+        h.ptr, R, pd.ptr, ud.ptr, B, tspan[1], tspan[2], ts, length(ts), od.ptr, opt, stats, stop, C_NULL)
+    check(h, st)
+    download!(out, od)
+    sol = u0 isa AbstractVector ? reshape(out, h.nin, length(ts), R) : out
+    return sol, stats, stop
+end
+
 # --- pruning a sparsified KAN (LV_driver_KANODE.jl:52-108): per-edge scores on the device, the keep rule and the
 # parameter slicing on the host.  Scores are Julia [O, I] matrices (the memory kanode_edge_scores writes).
 layer_length(h::Handle, i::Integer) = Int(ccall(sym(:kanode_layer_param_length), Int64, (Ptr{Cvoid}, Int32), h.ptr, i))

@@ -66,4 +66,33 @@ void ensemble_fill_args(const Args& shared, const EnsembleReplicas& e, const Ens
     }
 }
 
+// ---- the ensemble solve (kanode_solve_ensemble_tsit5, kan_ens_solve.hip) ----------------------------------------
+// R forward solves of one problem, workgroup r at p + r·P.  The handle's buffer of a call:
+//     status [R][4] int64 (naccept, nreject, nf, stop) | saveat [n_save] doubles | 64 spare bytes
+// both blocks at a multiple of 64 bytes; the Fisher-KPP field has besides one PP_PHI table per replica in a buffer
+// of its own, [R][table stride] doubles, every table at a multiple of 64 bytes.  The caller's arrays are dense:
+// p [R][P], u_save [R][n_save][n].
+constexpr int kEnsSolveStatusWords = 4;
+struct EnsSolveLayout {
+    size_t off_saveat, bytes;
+};
+inline EnsSolveLayout ens_solve_layout(int64_t R, int64_t n_save) {
+    EnsSolveLayout L;
+    L.off_saveat = ensemble_round((size_t)R * kEnsSolveStatusWords * sizeof(int64_t));
+    L.bytes = ensemble_round(L.off_saveat + (size_t)n_save * sizeof(double)) + 64;
+    return L;
+}
+// replica r's status words, in int64 words from the buffer's start
+inline size_t ens_solve_status_word(int64_t r) { return (size_t)r * kEnsSolveStatusWords; }
+// doubles between the tables of two replicas (coef coefficients of ni intervals each), and the whole buffer's bytes
+inline size_t ens_table_stride(int coef, int ni) {
+    return ensemble_round((size_t)coef * (size_t)ni * sizeof(double)) / sizeof(double);
+}
+inline size_t ens_table_bytes(int64_t R, int coef, int ni) { return (size_t)R * ens_table_stride(coef, ni) * sizeof(double); }
+// replica r's parameters and saveat rows, in elements from the start of p / u_save
+inline size_t ens_solve_p_elem(int64_t r, int64_t P) { return (size_t)r * (size_t)P; }
+inline size_t ens_solve_save_elem(int64_t r, int64_t n_save, int64_t n) {
+    return (size_t)r * (size_t)n_save * (size_t)n;
+}
+
 }  // namespace kan

@@ -618,6 +618,19 @@ constexpr int kChainSolveMaxBatch = 16;   // columns of one workgroup (256 lanes
 template <typename T>
 hipError_t launch_kd_chain_tsit5(const LayerConst* hlcs, int nl, const LayerConst* lcs, const T* p, int64_t P,
                                  const T* u0, int64_t B, const ChainSolveArgs& a, hipStream_t st);
+// The ensemble solve (kan_ens_solve.hip): n_rep (<= kTrainMaxReplicas) solves of one problem in one launch, workgroup
+// r the one-workgroup solve above (or launch_fk_small_tsit5's) at p + r·P, with u_save + r·n_save·n and out + 4r;
+// u0, saveat and the options shared, no dense output (a.rec null, a.cap 0).  The conditions are the single launchers'.
+// The Fisher-KPP entry first builds one PP_PHI table per replica into tables ([n_rep][table_stride] doubles, the
+// caller's, not the handle's stamped table): two launches for any n_rep.
+bool chain_tsit5_ens_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B, size_t esize);
+template <typename T>
+hipError_t launch_kd_chain_tsit5_ens(const LayerConst* hlcs, int nl, const LayerConst* lcs, const T* p, int64_t P,
+                                     const T* u0, int64_t B, const ChainSolveArgs& a, int64_t n_rep, hipStream_t st);
+hipError_t launch_fk_small_tsit5_ens(const LayerConst& hlc, const PPConst& hpc, const LayerConst* lc,
+                                     const PPConst* pc, const double* p, int64_t P, double* tables,
+                                     int64_t table_stride, const FkSmallArgs& s, const double* u0, int64_t B,
+                                     const ChainSolveArgs& a, int64_t n_rep, hipStream_t st);
 
 // surrogate shapes (kan_wide.hip)
 constexpr int kWideKT = 8;       // column tile of the wide-out kernels

@@ -100,6 +100,11 @@ struct kanode_handle {
     kan::DevBuf train_buf;
     std::vector<char> train_meta;
     size_t train_meta_off = 0;        // where in train_buf those bytes lie
+    // the ensemble solve (kanode_solve_ensemble_tsit5; kan_ensemble.hpp): status words | saveat, the host copy of
+    // the status words, and one PP_PHI table per replica (not dtable: that one, its stamps and built_phi stay as
+    // the single-replica paths left them).  Grow-only; kanode_reserve does not cover them.
+    kan::DevBuf ens_solve_buf, ens_tables;
+    kan::PinnedBuf ens_solve_host;
     // table reuse inside one integrator solve (p constant): build each table set once
     bool hold_tables = false;
     bool built_phi = false, built_vjp = false;
@@ -1969,6 +1974,52 @@ kanode_status kanode_internal_chain_tsit5(kanode_handle* h, const void* p, const
     if (e == hipErrorNotSupported) return KANODE_OK;
     if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string("launch_kd_chain_tsit5: ") + hipGetErrorString(e));
     launched = true;
+    return KANODE_OK;
+}
+// the ensemble solve: exactly what kanode_internal_chain_tsit5 launches for (kanode_internal_chain_tsit5_ok and the
+// launchers' own conditions)
+bool kanode_internal_solve_ens_ok(const kanode_handle* h, int64_t batch) {
+    if (!kanode_internal_chain_tsit5_ok(h, batch) || h->n_in != h->n_out) return false;
+    if (fk_small_ok(h, batch)) return h->hpc.ni % kan::kPPPerBlock == 0 && h->P >= h->hlc[0].G + 1;
+    return kan::chain_tsit5_ens_supported(h->hlc, h->n_layers, h->P, batch, h->esize);
+}
+kanode_status kanode_internal_solve_ens(kanode_handle* h, const void* p, int64_t R, const void* u0, int64_t batch,
+                                        kan::ChainSolveArgs* a, const double* saveat, int64_t n_save, int64_t* res,
+                                        void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const char* what = "kanode_solve_ensemble_tsit5";
+    const kan::EnsSolveLayout L = kan::ens_solve_layout(R, n_save);
+    const size_t res_bytes = (size_t)R * kan::kEnsSolveStatusWords * sizeof(int64_t);
+    const bool fk = fk_small_ok(h, batch);
+    const size_t stride = fk ? kan::ens_table_stride(kan::kPPCoef, h->hpc.ni) : 0;
+    const size_t tbytes = fk ? kan::ens_table_bytes(R, kan::kPPCoef, h->hpc.ni) : 0;
+    if (h->ens_solve_buf.bytes() < L.bytes || h->ens_tables.bytes() < tbytes || h->ens_solve_host.bytes() < res_bytes) {
+        HIP_TRY(h, hipStreamSynchronize(st));   // (an earlier call's kernels may still use the old buffers)
+        if (h->ens_solve_buf.reserve(L.bytes) != hipSuccess || h->ens_tables.reserve(tbytes) != hipSuccess ||
+            h->ens_solve_host.reserve(res_bytes) != hipSuccess)
+            return fail(h, KANODE_ERR_ALLOC, std::string(what) + ": out of memory for the replicas' status words and tables");
+    }
+    char* const base = h->ens_solve_buf.as<char>();
+    // (the call synchronises before it returns, so the caller's list outlives the copy)
+    HIP_TRY(h, hipMemcpyAsync(base + L.off_saveat, saveat, (size_t)n_save * sizeof(double), hipMemcpyHostToDevice, st));
+    a->saveat = reinterpret_cast<const double*>(base + L.off_saveat);
+    a->out = reinterpret_cast<int64_t*>(base);
+    hipError_t e;
+    if (fk)
+        e = kan::launch_fk_small_tsit5_ens(h->hlc[0], h->hpc, h->dlc(), h->dpc(), (const double*)p, h->P,
+                                           h->ens_tables.as<double>(), (int64_t)stride, fk_small_args(h),
+                                           (const double*)u0, batch, *a, R, st);
+    else if (h->spec.dtype == KANODE_F64)
+        e = kan::launch_kd_chain_tsit5_ens<double>(h->hlc, h->n_layers, h->dlc(), (const double*)p, h->P,
+                                                   (const double*)u0, batch, *a, R, st);
+    else
+        e = kan::launch_kd_chain_tsit5_ens<float>(h->hlc, h->n_layers, h->dlc(), (const float*)p, h->P,
+                                                  (const float*)u0, batch, *a, R, st);
+    if (e == hipErrorNotSupported) return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported");
+    if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(h->ens_solve_host.ptr(), base, res_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    std::memcpy(res, h->ens_solve_host.ptr(), res_bytes);
     return KANODE_OK;
 }
 kanode_status kanode_internal_vjp_stage(kanode_handle* h, const void* p, const void* u, const kanode_stage* state,

@@ -66,6 +66,14 @@ bool kanode_internal_chain_tsit5_ok(const kanode_handle* h, int64_t batch);
 int kanode_internal_fused_solve_cap(const kanode_handle* h);
 kanode_status kanode_internal_chain_tsit5(kanode_handle* h, const void* p, const void* u0, int64_t batch,
                                           const kan::ChainSolveArgs* a, void* stream, bool& launched);
+// the ensemble solve (kanode_solve_ensemble_tsit5; kan_ens_solve.hip): whether the handle takes it at this batch
+// (exactly where kanode_internal_chain_tsit5 launches), and the call: R replicas at p + r·P, a's saveat and out set
+// here (the handle's buffer; saveat is the host list), the per-replica tables of a Fisher-KPP field built first.
+// Synchronises; res = [R][4]: naccept, nreject, nf, status.  The handle's own table, stamps and built_phi are not touched.
+bool kanode_internal_solve_ens_ok(const kanode_handle* h, int64_t batch);
+kanode_status kanode_internal_solve_ens(kanode_handle* h, const void* p, int64_t R, const void* u0, int64_t batch,
+                                        kan::ChainSolveArgs* a, const double* saveat, int64_t n_save, int64_t* res,
+                                        void* stream);
 // a whole Tsit5 step per row on the Fisher-KPP table path (fk_step_pp_wave_kernel); launched =
 // false when the handle is not that path (the caller runs the six stages)
 // (q4x7: write the dense output as the interpolation polynomials Q_1..Q_4 and k_7)

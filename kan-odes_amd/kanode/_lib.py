@@ -114,6 +114,8 @@ OPTIONS = {"pointwise_table": OPT_POINTWISE_TABLE, "fused_step": OPT_FUSED_STEP,
            "fk_device_loop": OPT_FK_DEVICE_LOOP, "fsens_wide": OPT_FSENS_WIDE,
            "train_any_chain": OPT_TRAIN_ANY_CHAIN}
 
+SOLVE_STOP = {0: "ok", 1: "maxiters"}   # kanode_solve_stop
+
 _ENSEMBLE_ARGS = [_H, C.c_int64, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int64,
                   _P, C.c_double, C.POINTER(C.c_double), C.c_int64, _P, C.POINTER(SolverOptsC),
                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double,
@@ -142,6 +144,10 @@ SIGNATURES = [
     ("kanode_solution_step_sizes", C.c_int64, [_P, _P, _P, C.c_int64]),
     ("kanode_solve_tsit5", C.c_int, [_H, _P, _P, C.c_int64, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_int64,
                                      _P, C.POINTER(SolverOptsC), C.POINTER(C.c_void_p), C.POINTER(SolveStatsC), _P]),
+    ("kanode_solve_ensemble_supported", C.c_int32, [_H, C.c_int64]),
+    ("kanode_solve_ensemble_tsit5", C.c_int, [_H, C.c_int64, _P, _P, C.c_int64, C.c_double, C.c_double,
+                                              C.POINTER(C.c_double), C.c_int64, _P, C.POINTER(SolverOptsC),
+                                              C.POINTER(SolveStatsC), C.POINTER(C.c_int32), _P]),
     ("kanode_adjoint_tsit5", C.c_int, [_H, _P, _P, _P, _P, _P, C.POINTER(SolverOptsC), C.POINTER(SolveStatsC), _P]),
     ("kanode_adjoint_step_sizes", C.c_int64, [_H, _P, C.c_int64]),
     ("kanode_table_rejections", C.c_int, [_H, _P]),

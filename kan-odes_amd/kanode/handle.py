@@ -325,6 +325,36 @@ class KanodeHandle:
                 self._h, "kanode_solve_tsit5")
         return u_save, dict(naccept=st.naccept, nreject=st.nreject, nf=st.nf), dense
 
+    def solve_ensemble_supported(self, batch: int) -> bool:
+        """kanode_solve_ensemble_supported: the ensemble solve covers this handle at `batch` trajectories (exactly
+        where solve_tsit5 with control = auto runs as one workgroup)."""
+        return bool(L.lib().kanode_solve_ensemble_supported(self._h, int(batch)))
+
+    def solve_ensemble_tsit5(self, p: torch.Tensor, u0: torch.Tensor, t0: float, tf: float, saveat,
+                             opts: "L.SolverOptsC"):
+        """The solve of solve_tsit5 at every row of p [R, P] in one launch, one workgroup per replica
+        (kanode_solve_ensemble_tsit5): (u_save (R, len(saveat), *u0.shape), stats (R dicts), stop (R names of
+        _lib.SOLVE_STOP)).  u_save is pre-filled with NaN: a replica that reached maxiters ("maxiters", no
+        exception) leaves the rows past its last reached stop that way.  An unsupported shape or a bad argument raises
+        KanodeError."""
+        B = u0.shape[0] if u0.dim() == 2 else 1
+        if p.dim() != 2:
+            raise ValueError("solve_ensemble_tsit5 needs p of shape [R, P]")
+        R = int(p.shape[0])
+        self._check_t(p, (R, self.P), "p")
+        self._check_t(u0, None, "u0")
+        if u0.numel() != B * self.N or self.N_out != self.N:
+            raise ValueError("solve needs u0 of B x N entries and an RHS with N_in == N_out")
+        sv = self._saveat_c(saveat)
+        u_save = torch.full((R, len(saveat)) + tuple(u0.shape), float("nan"), dtype=self.dtype, device=self.device)
+        st = (L.SolveStatsC * max(R, 1))()
+        stop = (C.c_int32 * max(R, 1))()
+        L.check(L.lib().kanode_solve_ensemble_tsit5(self._h, R, _ptr(p), _ptr(u0), B, float(t0), float(tf), sv,
+                                                    len(saveat), _ptr(u_save), C.byref(opts), st, stop,
+                                                    _stream(self.device)), self._h, "kanode_solve_ensemble_tsit5")
+        stats = [dict(naccept=st[r].naccept, nreject=st[r].nreject, nf=st[r].nf) for r in range(R)]
+        return u_save, stats, [L.SOLVE_STOP.get(int(stop[r]), str(stop[r])) for r in range(R)]
+
     def _saveat_c(self, saveat):
         key = tuple(saveat)
         cache = self.__dict__.setdefault("_saveat_cache", {})

@@ -320,3 +320,72 @@ def solve(f, u0: torch.Tensor, tspan, p: torch.Tensor, saveat=None, opt: Tsit5Op
     else:
         raise RuntimeError("Tsit5: maxiters reached")
     return Solution(saveat[:len(out)], torch.stack(out), dict(naccept=naccept, nreject=nreject, nf=nf + 1))
+
+
+@dataclass
+class EnsembleSolution:
+    """solve_ensemble's result: t (the saveat list), u (R, len(t), *u0.shape), stats (R dicts), stop (R of "ok" /
+    "maxiters"; a stopped replica's rows of u are all NaN) and the path taken ("device": one launch per 4096
+    replicas, "host": a loop of solve())."""
+    t: list
+    u: torch.Tensor
+    stats: list
+    stop: list
+    path: str
+
+
+ENSEMBLE_SOLVE_MAX = 4096   # replicas of one kanode_solve_ensemble_tsit5 call (kTrainMaxReplicas)
+
+
+def solve_ensemble(f, u0: torch.Tensor, tspan, ps: torch.Tensor, saveat=None,
+                   opt: Tsit5Options | None = None) -> EnsembleSolution:
+    """solve(f, u0, tspan, ps[r], saveat, opt) for every row of ps [R, P], without gradients (the inputs are
+    detached): what an ensemble trained, a parameter sweep, a loss landscape.
+
+    Where solve() would run in libkanode and the handle covers the shape (KanodeHandle.solve_ensemble_supported: the
+    one-workgroup solves) all replicas go through ONE launch per 4096 replicas, one workgroup each, and row r has the
+    bits of solve() at ps[r].  Otherwise the host path: a loop of solve().  A replica whose solve reaches maxiters
+    does not raise on either path: stop[r] is "maxiters" and its rows of u are all NaN."""
+    from . import _lib as L
+    opt = opt or Tsit5Options()
+    if not isinstance(ps, torch.Tensor) or ps.dim() != 2 or ps.shape[0] < 1:
+        raise ValueError("solve_ensemble: ps must be a tensor of shape [R, P]")
+    t0, tf = float(tspan[0]), float(tspan[1])
+    saveat = _saveat_list(tspan, saveat)
+    u0, ps = u0.detach(), ps.detach()
+    R = int(ps.shape[0])
+    native = native_ok(f, u0, tspan, ps, saveat, opt)
+    if native:
+        tol = 1e-12 * max(1.0, abs(tf))
+        saveat = [s for s in saveat if s <= tf + tol]
+    B = u0.shape[0] if u0.dim() == 2 else 1
+    nan = float("nan")
+    with torch.no_grad():
+        if native and len(saveat) >= 1 and f.hd.solve_ensemble_supported(B):
+            psc, u0c, oc = ps.contiguous(), u0.contiguous(), opt.to_c()
+            us, stats, stop = [], [], []
+            for a in range(0, R, ENSEMBLE_SOLVE_MAX):
+                u, st, sp = f.hd.solve_ensemble_tsit5(psc[a:a + ENSEMBLE_SOLVE_MAX], u0c, t0, tf, saveat, oc)
+                us.append(u)
+                stats += st
+                stop += sp
+            u = us[0] if len(us) == 1 else torch.cat(us)
+            for r, s in enumerate(stop):
+                if s != "ok":
+                    u[r] = nan
+            return EnsembleSolution(list(saveat), u, stats, stop, "device")
+        u = torch.full((R, len(saveat)) + tuple(u0.shape), nan, dtype=u0.dtype, device=u0.device)
+        stats, stop = [], []
+        for r in range(R):
+            try:
+                sol = solve(f, u0, tspan, ps[r], saveat, opt)
+            except (RuntimeError, L.KanodeError) as e:   # (the Python loop's error, the native one)
+                if "maxiters" not in str(e):
+                    raise
+                stats.append({})
+                stop.append("maxiters")
+                continue
+            u[r, :sol.u.shape[0]] = sol.u
+            stats.append(sol.stats)
+            stop.append("ok")
+        return EnsembleSolution(list(saveat), u, stats, stop, "host")

@@ -23,7 +23,7 @@ from __future__ import annotations
 import torch
 
 from .adjoint import forward_ok, native_forward_dense, native_mse_gradient, native_mse_gradient_forward
-from .ode import Solution, Tsit5Options, _saveat_list, native_ok, solve
+from .ode import Solution, Tsit5Options, _saveat_list, native_ok, solve, solve_ensemble
 
 
 class Adam:
@@ -449,6 +449,7 @@ class EnsembleTrainer:
         self.sensealg = self._members[0].sensealg
         self.stopped = {}
         self.last_run = None      # "device_adjoint", "device_forward" or "host"
+        self.last_predict = None  # the path of the last predict() / eval_loss(): "device" or "host"
 
     @property
     def bp(self):
@@ -479,6 +480,23 @@ class EnsembleTrainer:
             raise ValueError("EnsembleTrainer.best: no live replica has a recorded loss")
         loss, r = min(cand)
         return r, loss
+
+    def predict(self, tspan=None, saveat=None):
+        """The trajectories of all R replicas at their current parameters (kanode.solve_ensemble: one launch where
+        the handle covers the problem), over the training span and saveat or the given ones, stopped replicas
+        included.  Returns an EnsembleSolution; last_predict records its path ("device" / "host").  Touches neither
+        p, m, v, the histories nor the members' cached forward."""
+        sol = solve_ensemble(self.rhs, self.u0, self.tspan if tspan is None else tspan, self.p,
+                             self.saveat if tspan is None and saveat is None else saveat, self.solver)
+        self.last_predict = sol.path
+        return sol
+
+    def eval_loss(self, test=None) -> list:
+        """mse_loss(u[r], target) of every replica at its current parameters, as R floats (NaN for a replica whose
+        solve reached maxiters): against the training target, or a held-out (tspan, saveat, target) triple."""
+        tspan, saveat, target = (None, None, self.target) if test is None else test
+        sol = self.predict(tspan, saveat)
+        return [float(mse_loss(sol.u[r], target)) for r in range(self.R)]
 
     def default_chunk(self, n_live: int) -> int:
         """The largest chunk with ceil(n_live / CUs) * chunk <= 256 (at least 1): workgroups beyond one per compute
