@@ -8,6 +8,7 @@
 // Parameter gradients: per-block LDS-staged tile products into a slab, then the
 // ordered slab reduction (bitwise reproducible; no float atomics).
 #include "kan_basis.hpp"
+#include "kan_chain_plan.hpp"
 #include "kan_common.hpp"
 #include "kan_kernels.hpp"
 #include "kan_onewg.hpp"
@@ -121,10 +122,6 @@ template <class S> __device__ __forceinline__ int sh_O(const LayerConst& lc, int
 template <class S> __device__ __forceinline__ int sh_G(const LayerConst& lc) {
     if constexpr (S::NL > 0) return S::GG;
     else return lc.G;
-}
-static bool chain_is_lv(const LayerConst* hlcs, int nl) {
-    return nl == 2 && hlcs[0].I == 2 && hlcs[0].O == 10 && hlcs[1].I == 10 && hlcs[1].O == 2 && hlcs[0].G == 5 &&
-           hlcs[1].G == 5;
 }
 
 // The forward of a whole small chain for one column group (16 lanes, lane j holds entry j of the
@@ -1055,50 +1052,6 @@ hipError_t launch_kd_edge_act(const LayerConst& hlc, const LayerConst* lc, const
     }
 }
 
-static bool I_ne_O(const LayerConst* hlcs, int nl) { return hlcs[0].I != hlcs[nl - 1].O; }
-
-// One launch for the whole chain when every layer is small (I, O <= 16), shares the
-// normalizer/path specialisation, the parameters fit in LDS and the batch is small enough
-// to be latency-bound; else returns hipErrorNotSupported and the caller runs one launch
-// per layer.
-template <typename T>
-hipError_t launch_kd_chain_col(const LayerConst* hlcs, int nl, const LayerConst* lcs, const T* p, int64_t P,
-                               const T* x, T* y, int64_t K, hipStream_t st, const StageArgs<T>* sa, T* y_out,
-                               double* err_slab, int slab_rows, double* err_out) {
-    // 16 lanes per column pays while the batch leaves the chip latency-bound (<= 32 columns
-    // per CU); beyond that the per-layer thread-per-column kernels keep every lane busy
-    if (nl < 1 || nl > 8 || K > 32768) return hipErrorNotSupported;
-    for (int l = 0; l < nl; ++l) {
-        const LayerConst& h = hlcs[l];
-        if (h.I > kChainDim || h.O > kChainDim || h.path != hlcs[0].path || h.norm != hlcs[0].norm)
-            return hipErrorNotSupported;
-        if (l > 0 && h.I != hlcs[l - 1].O) return hipErrorNotSupported;
-    }
-    const size_t lds = nl * sizeof(LayerConst) + (size_t)P * sizeof(T);
-    if (lds > 48 * 1024) return hipErrorNotSupported;
-    if (sa && I_ne_O(hlcs, nl)) return hipErrorNotSupported;
-    const StageArgs<T> none{};
-    const StageArgs<T>& s = sa ? *sa : none;
-    const int g = grid_for(K * kChainDim, kChainBlock, err_out ? (slab_rows < kGridCap ? slab_rows : kGridCap) : kGridCap);
-    const bool one = g == 1;
-    double* es = err_out && !one ? err_slab : nullptr;
-    double* ed = err_out && one ? err_out : nullptr;
-    const LayerConst& h = hlcs[0];
-#define KAN_CHAIN_S(NORM, PATH, S)                                                                                    \
-    hipLaunchKernelGGL((kd_chain_col_kernel<T, NORM, PATH, S>), dim3(g), dim3(kChainBlock), lds, st, lcs, nl, p,     \
-                       (int)P, x, y, K, s, y_out, es, ed)
-    if (h.norm == NORM_TANH_FAST && h.path == PATH_REC && chain_is_lv(hlcs, nl))
-        KAN_CHAIN_S(NORM_TANH_FAST, PATH_REC, ChainShapeLV);
-    else if (h.norm == NORM_TANH_FAST && h.path == PATH_REC) KAN_CHAIN_S(NORM_TANH_FAST, PATH_REC, ChainShapeAny);
-    else if (h.path == PATH_REC_CORR) KAN_CHAIN_S(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny);
-    else if (h.path == PATH_REC) KAN_CHAIN_S(NORM_RUNTIME, PATH_REC, ChainShapeAny);
-    else KAN_CHAIN_S(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny);
-#undef KAN_CHAIN_S
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || !es) return e;
-    return launch_stage_error_final(err_slab, g, err_out, st);
-}
-
 // The InterpolatingAdjoint of a small chain in ONE workgroup (kanode_adjoint_tsit5 after a
 // kd_chain_tsit5_kernel forward): the backward Tsit5 over [λ; μ] with the steps, stops, jumps,
 // FSAL re-evaluation and controller of kanode_solve.cpp adjoint_t.  Column group g holds λ of
@@ -1222,13 +1175,6 @@ kd_chain_adjoint_kernel(const LayerConst* __restrict__ lcs, int nl, const T* __r
 // one lane's single product: kμ needs no reduction at all.  Seven block barriers per adjoint stage.
 constexpr int kWideF1 = 16;   // layer-1 features per hidden unit (one DPP row)
 constexpr int kWideF2 = 64;   // layer-2 features per output (one wave)
-struct WideShape {
-    int I, H, O, G1, G2;
-};
-__host__ __device__ inline bool wide_fits(const WideShape& w) {
-    return w.I >= 1 && w.O >= 1 && w.I == w.O && w.H <= kChainBlock / kWideF1 && w.I * (w.G1 + 1) <= kWideF1 &&
-           w.H * (w.G2 + 1) <= kWideF2 && w.O <= kChainBlock / kWave;
-}
 
 // One feature of a layer at input value x: c < G -> basis g = c of N(x), c == G -> swish(x).  feat, and the
 // rrule factors: for a basis the pullback factor -2·y·φ (times φ̄·invh later), for swish swish'(x).
@@ -1956,104 +1902,107 @@ kd_chain_adjoint_lvsp_kernel(const LayerConst* __restrict__ lcs, const double* _
     }
 }
 
-// one Lotka-Volterra trajectory on the LvWaveModel kernels (the lvsp / lvwave adjoints, the fused training loop)
-static bool chain_is_lv_wave(const LayerConst* hlcs, int nl, int64_t B, bool wide) {
-    return wide && B == 1 && nl == 2 && hlcs[0].use_base && hlcs[1].use_base && hlcs[0].norm == hlcs[1].norm &&
-           hlcs[0].I == LvWaveShape::I && hlcs[0].O == LvWaveShape::H && hlcs[1].I == LvWaveShape::H &&
-           hlcs[1].O == LvWaveShape::O && hlcs[0].G == LvWaveShape::G && hlcs[1].G == LvWaveShape::G &&
-           hlcs[0].basis == BASIS_RBF && hlcs[1].basis == BASIS_RBF &&
-           (hlcs[0].norm == NORM_TANH_FAST || hlcs[0].norm == NORM_SOFTSIGN);
+// kan_chain_plan.hpp's view of the device classes above: the shape predicates, the ladder's rung and the plan of the
+// one-workgroup adjoint are decided there from these numbers
+constexpr ChainLimits kChainLimits{kChainDim, kChainBlock, kWave, kMaxLayers, kChainMaxLayers, kChainSolveMaxBatch,
+                                   kChainAdjointMaxSteps, kWideF1, kWideF2, WideModel<double, NORM_SOFTSIGN>::kEnd,
+                                   LvWaveShape::I, LvWaveShape::H, LvWaveShape::O, LvWaveShape::G, kLvP, KAN_LV_SP,
+                                   kLvSpWaves, sizeof(LayerConst), NORM_TANH_FAST, NORM_SOFTSIGN, PATH_REC,
+                                   PATH_REC_CORR, BASIS_RBF};
+static_assert(WideModel<float, NORM_TANH_FAST>::kEnd == kChainLimits.wide_end, "one scratch size for every WideModel");
+
+// The specialisation ladder of the small-chain kernels: go(norm, path, shape) with the rung's NORM and PATH as
+// integral constants and its shape class as a value; a launcher's go holds its own launch and nothing else.
+template <class Go>
+auto chain_ladder(const LayerConst* hlcs, int nl, Go&& go) {
+    switch (chain_rung(kChainLimits, hlcs, nl)) {
+    case kRungLV: return go(ITag<NORM_TANH_FAST>{}, ITag<PATH_REC>{}, ChainShapeLV{});
+    case kRungTanhRec: return go(ITag<NORM_TANH_FAST>{}, ITag<PATH_REC>{}, ChainShapeAny{});
+    case kRungRecCorr: return go(ITag<NORM_RUNTIME>{}, ITag<PATH_REC_CORR>{}, ChainShapeAny{});
+    case kRungRec: return go(ITag<NORM_RUNTIME>{}, ITag<PATH_REC>{}, ChainShapeAny{});
+    default: return go(ITag<NORM_RUNTIME>{}, ITag<PATH_DIRECT>{}, ChainShapeAny{});
+    }
 }
 
 // (kan_train.hip includes this file for the device code above and instantiates none of the launchers below)
 #ifndef KAN_COL_DEVICE_ONLY
-// The one-workgroup adjoint (kd_chain_adjoint_kernel): the small-chain conditions of
-// launch_kd_chain_tsit5 plus nsteps <= kChainAdjointMaxSteps and the LDS budget.
+// One launch for the whole chain when every layer is small (I, O <= 16), shares the
+// normalizer/path specialisation, the parameters fit in LDS and the batch is small enough
+// to be latency-bound; else returns hipErrorNotSupported and the caller runs one launch
+// per layer.
+template <typename T>
+hipError_t launch_kd_chain_col(const LayerConst* hlcs, int nl, const LayerConst* lcs, const T* p, int64_t P,
+                               const T* x, T* y, int64_t K, hipStream_t st, const StageArgs<T>* sa, T* y_out,
+                               double* err_slab, int slab_rows, double* err_out) {
+    // 16 lanes per column pays while the batch leaves the chip latency-bound (<= 32 columns
+    // per CU); beyond that the per-layer thread-per-column kernels keep every lane busy
+    if (K > 32768 || !chain_small_layers(kChainLimits, hlcs, nl, kChainLimits.fwd_layers) ||
+        !chain_params_fit(kChainLimits, nl, P, sizeof(T)) || (sa && I_ne_O(hlcs, nl)))
+        return hipErrorNotSupported;
+    const size_t lds = chain_param_lds(kChainLimits, nl, P, sizeof(T));
+    const StageArgs<T> none{};
+    const StageArgs<T>& s = sa ? *sa : none;
+    const int g = grid_for(K * kChainDim, kChainBlock, err_out ? (slab_rows < kGridCap ? slab_rows : kGridCap) : kGridCap);
+    const bool one = g == 1;
+    double* es = err_out && !one ? err_slab : nullptr;
+    double* ed = err_out && one ? err_out : nullptr;
+    chain_ladder(hlcs, nl, [&](auto norm, auto path, auto shape) {
+        hipLaunchKernelGGL((kd_chain_col_kernel<T, norm(), path(), decltype(shape)>), dim3(g), dim3(kChainBlock), lds, st,
+                           lcs, nl, p, (int)P, x, y, K, s, y_out, es, ed);
+    });
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !es) return e;
+    return launch_stage_error_final(err_slab, g, err_out, st);
+}
+
+// The one-workgroup adjoint on the model, block and dynamic LDS of chain_adjoint_plan (kan_chain_plan.hpp);
+// hipErrorNotSupported where no model fits.
 template <typename T>
 hipError_t launch_kd_chain_adjoint(const LayerConst* hlcs, int nl, const LayerConst* lcs, const T* p, int64_t P,
                                    int64_t B, const ChainAdjointArgs& a, hipStream_t st, bool wide) {
-    if (nl < 1 || nl > kChainMaxLayers || B < 1 || B > kChainSolveMaxBatch || I_ne_O(hlcs, nl) || a.nsteps < 1 ||
-        a.nsteps > kChainAdjointMaxSteps)
-        return hipErrorNotSupported;
-    // one Lotka-Volterra trajectory: the chain on one wave (LvWaveModel)
-    if (chain_is_lv_wave(hlcs, nl, B, wide)) {
-        const size_t pre = 2 * sizeof(LayerConst) + sizeof(T) * (size_t)P * 10;   // ps, μ [2], kμ [7]
-        size_t lds = pre + 2 * sizeof(double) * a.nsteps;
-        const size_t rec = sizeof(T) * ((size_t)a.nsteps * 7 + 1) * LvWaveShape::I;
-        const int stage_rec = lds + rec <= 60 * 1024 ? 1 : 0;
-        if (stage_rec) lds += rec;
-        if constexpr (std::is_same<T, double>::value) {   // the stage-parallel form (kd_chain_adjoint_lvsp_kernel)
-            const size_t jst = sizeof(double) * 8 * LvWaveShape::I * (kLvP + LvWaveShape::I);
-            size_t lsp = 2 * sizeof(LayerConst) + sizeof(double) * (kLvP + 2 * (size_t)a.nsteps);
-            const int sp_rec = lsp + rec + jst <= 140 * 1024 ? 1 : 0;
-            if (sp_rec) lsp += rec;
-            if (KAN_LV_SP && P == kLvP && lsp + jst <= 140 * 1024) {
-                const void* fn = hlcs[0].norm == NORM_TANH_FAST
-                                     ? reinterpret_cast<const void*>(&kd_chain_adjoint_lvsp_kernel<NORM_TANH_FAST>)
-                                     : reinterpret_cast<const void*>(&kd_chain_adjoint_lvsp_kernel<NORM_SOFTSIGN>);
-                {
-                    const hipError_t e = ensure_dynamic_lds(fn, lsp);
-                    if (e != hipSuccess) return e;
-                }
-                if (hlcs[0].norm == NORM_TANH_FAST)
-                    hipLaunchKernelGGL((kd_chain_adjoint_lvsp_kernel<NORM_TANH_FAST>), dim3(1), dim3((kLvSpWaves + 1) * kWave),
-                                       lsp, st, lcs, p, a, sp_rec);
-                else
-                    hipLaunchKernelGGL((kd_chain_adjoint_lvsp_kernel<NORM_SOFTSIGN>), dim3(1), dim3((kLvSpWaves + 1) * kWave),
-                                       lsp, st, lcs, p, a, sp_rec);
-                return hipGetLastError();
-            }
-        }
-        if (pre % 8 == 0 && lds <= 60 * 1024) {
-            if (hlcs[0].norm == NORM_TANH_FAST)
-                hipLaunchKernelGGL((kd_chain_adjoint_lvwave_kernel<T, NORM_TANH_FAST>), dim3(1), dim3(kWave), lds, st,
-                                   lcs, p, (int)P, a, stage_rec);
+    const ChainAdjPlan plan = chain_adjoint_plan(kChainLimits, hlcs, nl, P, B, wide, a.nsteps, sizeof(T));
+    const bool tf = hlcs[0].norm == NORM_TANH_FAST;   // (the wave and workgroup models: tanh_fast or softsign)
+    const dim3 block(plan.threads);
+    const size_t lds = plan.lds;
+    switch (plan.model) {
+    case kAdjLvSp:   // one Lotka-Volterra trajectory, the stages of a step on a wave each (fp64)
+        if constexpr (std::is_same<T, double>::value) {
+            const void* fn = tf ? reinterpret_cast<const void*>(&kd_chain_adjoint_lvsp_kernel<NORM_TANH_FAST>)
+                                : reinterpret_cast<const void*>(&kd_chain_adjoint_lvsp_kernel<NORM_SOFTSIGN>);
+            const hipError_t e = ensure_dynamic_lds(fn, lds);
+            if (e != hipSuccess) return e;
+            if (tf)
+                hipLaunchKernelGGL((kd_chain_adjoint_lvsp_kernel<NORM_TANH_FAST>), dim3(1), block, lds, st, lcs, p, a,
+                                   plan.stage_rec);
             else
-                hipLaunchKernelGGL((kd_chain_adjoint_lvwave_kernel<T, NORM_SOFTSIGN>), dim3(1), dim3(kWave), lds, st,
-                                   lcs, p, (int)P, a, stage_rec);
-            return hipGetLastError();
+                hipLaunchKernelGGL((kd_chain_adjoint_lvsp_kernel<NORM_SOFTSIGN>), dim3(1), block, lds, st, lcs, p, a,
+                                   plan.stage_rec);
         }
+        break;
+    case kAdjLvWave:   // one Lotka-Volterra trajectory: the chain on one wave (LvWaveModel)
+        if (tf)
+            hipLaunchKernelGGL((kd_chain_adjoint_lvwave_kernel<T, NORM_TANH_FAST>), dim3(1), block, lds, st, lcs, p,
+                               (int)P, a, plan.stage_rec);
+        else
+            hipLaunchKernelGGL((kd_chain_adjoint_lvwave_kernel<T, NORM_SOFTSIGN>), dim3(1), block, lds, st, lcs, p,
+                               (int)P, a, plan.stage_rec);
+        break;
+    case kAdjWide:   // one trajectory of a two-layer chain with base activations: the whole workgroup on it (WideModel)
+        if (tf)
+            hipLaunchKernelGGL((kd_chain_adjoint_wide_kernel<T, NORM_TANH_FAST>), dim3(1), block, lds, st, lcs, p,
+                               (int)P, a, plan.stage_rec);
+        else
+            hipLaunchKernelGGL((kd_chain_adjoint_wide_kernel<T, NORM_SOFTSIGN>), dim3(1), block, lds, st, lcs, p,
+                               (int)P, a, plan.stage_rec);
+        break;
+    case kAdjChain:   // a column group per trajectory (ChainModel)
+        chain_ladder(hlcs, nl, [&](auto norm, auto path, auto shape) {
+            hipLaunchKernelGGL((kd_chain_adjoint_kernel<T, norm(), path(), decltype(shape)>), dim3(1), block, lds, st,
+                               lcs, nl, p, (int)P, B, a);
+        });
+        break;
+    default: return hipErrorNotSupported;
     }
-    // one trajectory of a two-layer chain with base activations: the whole workgroup on it (WideModel)
-    if (wide && B == 1 && nl == 2 && hlcs[0].use_base && hlcs[1].use_base && hlcs[0].norm == hlcs[1].norm &&
-        hlcs[1].I == hlcs[0].O && wide_fits(WideShape{hlcs[0].I, hlcs[0].O, hlcs[1].O, hlcs[0].G, hlcs[1].G}) &&
-        (hlcs[0].norm == NORM_TANH_FAST || hlcs[0].norm == NORM_SOFTSIGN)) {
-        const size_t pre = 2 * sizeof(LayerConst) + sizeof(T) * ((size_t)P * 10 + WideModel<T, NORM_SOFTSIGN>::kEnd);
-        size_t lds = pre + 2 * sizeof(double) * a.nsteps;
-        const size_t rec = sizeof(T) * ((size_t)a.nsteps * 7 + 1) * hlcs[0].I;   // the dense output, staged
-        const int stage_rec = lds + rec <= 60 * 1024 ? 1 : 0;
-        if (stage_rec) lds += rec;
-        if (pre % 8 == 0 && lds <= 60 * 1024) {
-            if (hlcs[0].norm == NORM_TANH_FAST)
-                hipLaunchKernelGGL((kd_chain_adjoint_wide_kernel<T, NORM_TANH_FAST>), dim3(1), dim3(kChainBlock), lds, st,
-                                   lcs, p, (int)P, a, stage_rec);
-            else
-                hipLaunchKernelGGL((kd_chain_adjoint_wide_kernel<T, NORM_SOFTSIGN>), dim3(1), dim3(kChainBlock), lds, st,
-                                   lcs, p, (int)P, a, stage_rec);
-            return hipGetLastError();
-        }
-    }
-    for (int l = 0; l < nl; ++l) {
-        const LayerConst& h = hlcs[l];
-        if (h.I > kChainDim || h.O > kChainDim || h.path != hlcs[0].path || h.norm != hlcs[0].norm)
-            return hipErrorNotSupported;
-        if (l > 0 && h.I != hlcs[l - 1].O) return hipErrorNotSupported;
-    }
-    const int threads = (int)((B * kChainDim + kWave - 1) / kWave) * kWave;
-    const int NG = threads / kChainDim;
-    const size_t lds = nl * sizeof(LayerConst) + (size_t)P * sizeof(T) * (1 + NG + 9) + 2 * sizeof(double) * a.nsteps + 16;
-    if (lds > 60 * 1024 || (P * sizeof(T)) % 8) return hipErrorNotSupported;
-    const LayerConst& h = hlcs[0];
-#define KAN_CADJ_S(NORM, PATH, S)                                                                                     \
-    hipLaunchKernelGGL((kd_chain_adjoint_kernel<T, NORM, PATH, S>), dim3(1), dim3(threads), lds, st, lcs, nl, p,     \
-                       (int)P, B, a)
-    if (h.norm == NORM_TANH_FAST && h.path == PATH_REC && chain_is_lv(hlcs, nl))
-        KAN_CADJ_S(NORM_TANH_FAST, PATH_REC, ChainShapeLV);
-    else if (h.norm == NORM_TANH_FAST && h.path == PATH_REC) KAN_CADJ_S(NORM_TANH_FAST, PATH_REC, ChainShapeAny);
-    else if (h.path == PATH_REC_CORR) KAN_CADJ_S(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny);
-    else if (h.path == PATH_REC) KAN_CADJ_S(NORM_RUNTIME, PATH_REC, ChainShapeAny);
-    else KAN_CADJ_S(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny);
-#undef KAN_CADJ_S
     return hipGetLastError();
 }
 
@@ -2062,27 +2011,13 @@ hipError_t launch_kd_chain_adjoint(const LayerConst* hlcs, int nl, const LayerCo
 template <typename T>
 hipError_t launch_kd_chain_tsit5(const LayerConst* hlcs, int nl, const LayerConst* lcs, const T* p, int64_t P,
                                  const T* u0, int64_t B, const ChainSolveArgs& a, hipStream_t st) {
-    if (nl < 1 || nl > 8 || B < 1 || B > kChainSolveMaxBatch || I_ne_O(hlcs, nl)) return hipErrorNotSupported;
-    for (int l = 0; l < nl; ++l) {
-        const LayerConst& h = hlcs[l];
-        if (h.I > kChainDim || h.O > kChainDim || h.path != hlcs[0].path || h.norm != hlcs[0].norm)
-            return hipErrorNotSupported;
-        if (l > 0 && h.I != hlcs[l - 1].O) return hipErrorNotSupported;
-    }
-    const size_t lds = nl * sizeof(LayerConst) + (size_t)P * sizeof(T);
-    if (lds > 48 * 1024) return hipErrorNotSupported;
-    const int threads = (int)((B * kChainDim + kWave - 1) / kWave) * kWave;
-    const LayerConst& h = hlcs[0];
-#define KAN_CSOLVE_S(NORM, PATH, S)                                                                                   \
-    hipLaunchKernelGGL((kd_chain_tsit5_kernel<T, NORM, PATH, S>), dim3(1), dim3(threads), lds, st, lcs, nl, p, (int)P, \
-                       u0, B, a)
-    if (h.norm == NORM_TANH_FAST && h.path == PATH_REC && chain_is_lv(hlcs, nl))
-        KAN_CSOLVE_S(NORM_TANH_FAST, PATH_REC, ChainShapeLV);
-    else if (h.norm == NORM_TANH_FAST && h.path == PATH_REC) KAN_CSOLVE_S(NORM_TANH_FAST, PATH_REC, ChainShapeAny);
-    else if (h.path == PATH_REC_CORR) KAN_CSOLVE_S(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny);
-    else if (h.path == PATH_REC) KAN_CSOLVE_S(NORM_RUNTIME, PATH_REC, ChainShapeAny);
-    else KAN_CSOLVE_S(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny);
-#undef KAN_CSOLVE_S
+    if (!chain_tsit5_shape(kChainLimits, hlcs, nl, P, B, sizeof(T))) return hipErrorNotSupported;
+    const size_t lds = chain_param_lds(kChainLimits, nl, P, sizeof(T));
+    const int threads = chain_threads(kChainLimits, B);
+    chain_ladder(hlcs, nl, [&](auto norm, auto path, auto shape) {
+        hipLaunchKernelGGL((kd_chain_tsit5_kernel<T, norm(), path(), decltype(shape)>), dim3(1), dim3(threads), lds, st,
+                           lcs, nl, p, (int)P, u0, B, a);
+    });
     return hipGetLastError();
 }
 
@@ -2092,28 +2027,16 @@ template <typename T>
 hipError_t launch_kd_chain_step(const LayerConst* hlcs, int nl, const LayerConst* lcs, const T* p, int64_t P,
                                 int64_t K, const ChainStepArgs& a, double* err_slab, int slab_rows, double* err_out,
                                 hipStream_t st) {
-    if (nl < 1 || nl > 8 || K > 32768 || I_ne_O(hlcs, nl)) return hipErrorNotSupported;
-    for (int l = 0; l < nl; ++l) {
-        const LayerConst& h = hlcs[l];
-        if (h.I > kChainDim || h.O > kChainDim || h.path != hlcs[0].path || h.norm != hlcs[0].norm)
-            return hipErrorNotSupported;
-        if (l > 0 && h.I != hlcs[l - 1].O) return hipErrorNotSupported;
-    }
-    const size_t lds = nl * sizeof(LayerConst) + (size_t)P * sizeof(T);
-    if (lds > 48 * 1024) return hipErrorNotSupported;
+    if (K > 32768 || !chain_small_layers(kChainLimits, hlcs, nl, kChainLimits.fwd_layers) || I_ne_O(hlcs, nl) ||
+        !chain_params_fit(kChainLimits, nl, P, sizeof(T)))
+        return hipErrorNotSupported;
+    const size_t lds = chain_param_lds(kChainLimits, nl, P, sizeof(T));
     const int g = grid_for(K * kChainDim, kChainBlock, slab_rows < kGridCap ? slab_rows : kGridCap);
     double* es = err_out ? err_slab : nullptr;
-    const LayerConst& h = hlcs[0];
-#define KAN_CSTEP(NORM, PATH, S)                                                                                 \
-    hipLaunchKernelGGL((kd_chain_step_kernel<T, NORM, PATH, S>), dim3(g), dim3(kChainBlock), lds, st, lcs, nl, p,  \
-                       (int)P, K, a, es)
-    if (h.norm == NORM_TANH_FAST && h.path == PATH_REC && chain_is_lv(hlcs, nl))
-        KAN_CSTEP(NORM_TANH_FAST, PATH_REC, ChainShapeLV);
-    else if (h.norm == NORM_TANH_FAST && h.path == PATH_REC) KAN_CSTEP(NORM_TANH_FAST, PATH_REC, ChainShapeAny);
-    else if (h.path == PATH_REC_CORR) KAN_CSTEP(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny);
-    else if (h.path == PATH_REC) KAN_CSTEP(NORM_RUNTIME, PATH_REC, ChainShapeAny);
-    else KAN_CSTEP(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny);
-#undef KAN_CSTEP
+    chain_ladder(hlcs, nl, [&](auto norm, auto path, auto shape) {
+        hipLaunchKernelGGL((kd_chain_step_kernel<T, norm(), path(), decltype(shape)>), dim3(g), dim3(kChainBlock), lds, st,
+                           lcs, nl, p, (int)P, K, a, es);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !es) return e;
     return launch_stage_error_final(err_slab, g, err_out, st);
@@ -2127,13 +2050,7 @@ size_t chain_vjp_step_slab_bytes(int64_t P, int64_t K, size_t esize, int grid_ca
     return 7 * (((size_t)grid * P * esize + 255) & ~(size_t)255) + (size_t)grid * sizeof(double) + 256;
 }
 bool chain_vjp_step_supported(const LayerConst* hlcs, int nl, int64_t P, size_t esize) {
-    if (nl < 1 || nl > kChainMaxLayers) return false;
-    for (int l = 0; l < nl; ++l) {
-        const LayerConst& h = hlcs[l];
-        if (h.I > kChainDim || h.O > kChainDim || h.path != hlcs[0].path || h.norm != hlcs[0].norm) return false;
-        if (l > 0 && h.I != hlcs[l - 1].O) return false;
-    }
-    if (hlcs[nl - 1].O != hlcs[0].I) return false;
+    if (!chain_small_layers(kChainLimits, hlcs, nl, kChainLimits.vjp_layers) || I_ne_O(hlcs, nl)) return false;
     return nl * sizeof(LayerConst) + (size_t)P * esize * (1 + 7 * (kChainVjpBlock / kChainDim)) <= 64 * 1024;
 }
 
@@ -2152,17 +2069,10 @@ hipError_t launch_kd_chain_vjp_step(const LayerConst* hlcs, int nl, const LayerC
     const int64_t region = (int64_t)((((size_t)grid * P * sizeof(T) + 255) & ~(size_t)255) / sizeof(T));
     T* tslab = (T*)slab;
     double* eslab = (double*)((char*)slab + 7 * region * sizeof(T));
-    const LayerConst& h = hlcs[0];
-#define KAN_CVSTEP(NORM, PATH, S)                                                                                 \
-    hipLaunchKernelGGL((kd_chain_vjp_step_kernel<T, NORM, PATH, S>), dim3(grid), dim3(kChainVjpBlock), lds, st,  \
-                       lcs, nl, p, (int)P, K, a, tslab, region, eslab)
-    if (h.norm == NORM_TANH_FAST && h.path == PATH_REC && chain_is_lv(hlcs, nl))
-        KAN_CVSTEP(NORM_TANH_FAST, PATH_REC, ChainShapeLV);
-    else if (h.norm == NORM_TANH_FAST && h.path == PATH_REC) KAN_CVSTEP(NORM_TANH_FAST, PATH_REC, ChainShapeAny);
-    else if (h.path == PATH_REC_CORR) KAN_CVSTEP(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny);
-    else if (h.path == PATH_REC) KAN_CVSTEP(NORM_RUNTIME, PATH_REC, ChainShapeAny);
-    else KAN_CVSTEP(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny);
-#undef KAN_CVSTEP
+    chain_ladder(hlcs, nl, [&](auto norm, auto path, auto shape) {
+        hipLaunchKernelGGL((kd_chain_vjp_step_kernel<T, norm(), path(), decltype(shape)>), dim3(grid),
+                           dim3(kChainVjpBlock), lds, st, lcs, nl, p, (int)P, K, a, tslab, region, eslab);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     ChainKmOut<T> km{};
@@ -2178,14 +2088,8 @@ hipError_t launch_kd_chain_vjp_stage(const LayerConst* hlcs, int nl, const Layer
                                      const T* u, const StageArgs<T>& su, const T* lam, const StageArgs<T>& sl,
                                      T* lam_out, T* lamJ, T* dp, bool dp_assign, double* err_out, void* slab,
                                      size_t slab_bytes, int64_t K, hipStream_t st) {
-    if (nl < 1 || nl > kChainMaxLayers || K < 1) return hipErrorNotSupported;
-    for (int l = 0; l < nl; ++l) {
-        const LayerConst& h = hlcs[l];
-        if (h.I > kChainDim || h.O > kChainDim || h.path != hlcs[0].path || h.norm != hlcs[0].norm)
-            return hipErrorNotSupported;
-        if (l > 0 && h.I != hlcs[l - 1].O) return hipErrorNotSupported;
-    }
-    if (hlcs[nl - 1].O != hlcs[0].I) return hipErrorNotSupported;
+    if (K < 1 || !chain_small_layers(kChainLimits, hlcs, nl, kChainLimits.vjp_layers) || I_ne_O(hlcs, nl))
+        return hipErrorNotSupported;
     const int ng = kChainVjpBlock / kChainDim;
     const size_t lds = nl * sizeof(LayerConst) + (size_t)P * sizeof(T) * (1 + ng);
     if (lds > 60 * 1024) return hipErrorNotSupported;
@@ -2196,19 +2100,13 @@ hipError_t launch_kd_chain_vjp_stage(const LayerConst* hlcs, int nl, const Layer
     const int grid = grid_for(K, ng, (int)cap);
     T* tslab = (T*)slab;
     double* eslab = err_out ? (double*)((char*)slab + (((size_t)grid * P * sizeof(T) + 255) & ~(size_t)255)) : nullptr;
-    const LayerConst& h = hlcs[0];
     const bool one = grid == 1;   // a single block writes dp and the error total itself
-#define KAN_CVJP(NORM, PATH, S)                                                                                  \
-    hipLaunchKernelGGL((kd_chain_vjp_stage_kernel<T, NORM, PATH, S>), dim3(grid), dim3(kChainVjpBlock), lds, st, \
-                       lcs, nl, p, (int)P, u, su, lam, sl, lam_out, lamJ, one ? nullptr : tslab,                  \
-                       one ? nullptr : eslab, K, one ? dp : nullptr, dp_assign ? 1 : 0, one ? err_out : nullptr)
-    if (h.norm == NORM_TANH_FAST && h.path == PATH_REC && chain_is_lv(hlcs, nl))
-        KAN_CVJP(NORM_TANH_FAST, PATH_REC, ChainShapeLV);
-    else if (h.norm == NORM_TANH_FAST && h.path == PATH_REC) KAN_CVJP(NORM_TANH_FAST, PATH_REC, ChainShapeAny);
-    else if (h.path == PATH_REC_CORR) KAN_CVJP(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny);
-    else if (h.path == PATH_REC) KAN_CVJP(NORM_RUNTIME, PATH_REC, ChainShapeAny);
-    else KAN_CVJP(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny);
-#undef KAN_CVJP
+    chain_ladder(hlcs, nl, [&](auto norm, auto path, auto shape) {
+        hipLaunchKernelGGL((kd_chain_vjp_stage_kernel<T, norm(), path(), decltype(shape)>), dim3(grid),
+                           dim3(kChainVjpBlock), lds, st, lcs, nl, p, (int)P, u, su, lam, sl, lam_out, lamJ,
+                           one ? nullptr : tslab, one ? nullptr : eslab, K, one ? dp : nullptr, dp_assign ? 1 : 0,
+                           one ? err_out : nullptr);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || one || (!dp && !err_out)) return e;
     hipLaunchKernelGGL((chain_vjp_finish_kernel<T>), dim3((unsigned)(dp ? P : 0) + (err_out ? 1 : 0)), dim3(kBlock), 0,

@@ -33,6 +33,10 @@ constexpr int kBlock = 256;
 constexpr int kWave = 64;
 constexpr int kGridCap = 256 * 16;   // 16 blocks per CU over 256 CUs; grid-stride beyond
 
+// A kernel template argument as a value: a launcher's specialisation ladder hands these to the launcher's generic
+// lambda, which reads them back as constants (norm(), path(), ...)
+template <int V> using ITag = std::integral_constant<int, V>;
+
 // DPP lane permutations (VALU, no LDS round trip) of a 32/64-bit value
 template <int CTRL> __device__ __forceinline__ double dpp_mov(double v) {
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);

@@ -111,37 +111,23 @@ fk_small_tsit5_ens_kernel(const LayerConst* __restrict__ lcp, const double* __re
 
 }  // namespace
 
-// launch_kd_chain_tsit5's conditions (no launch): every layer small, one normalizer / path specialisation,
-// N_in == N_out, B <= kChainSolveMaxBatch, the constants and parameters within the LDS budget
+// whether the ensemble solve covers this chain (no launch): the shapes of the one-workgroup solve
 bool chain_tsit5_ens_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B, size_t esize) {
-    if (nl < 1 || nl > 8 || B < 1 || B > kChainSolveMaxBatch || I_ne_O(hlcs, nl)) return false;
-    for (int l = 0; l < nl; ++l) {
-        const LayerConst& h = hlcs[l];
-        if (h.I > kChainDim || h.O > kChainDim || h.path != hlcs[0].path || h.norm != hlcs[0].norm) return false;
-        if (l > 0 && h.I != hlcs[l - 1].O) return false;
-    }
-    return nl * sizeof(LayerConst) + (size_t)P * esize <= 48 * 1024;
+    return chain_tsit5_shape(kChainLimits, hlcs, nl, P, B, esize);
 }
 
-// launch_kd_chain_tsit5's conditions, block, dynamic LDS and specialisation ladder, on a grid of n_rep workgroups
+// the one-workgroup solve's block and dynamic LDS on a grid of n_rep workgroups
 template <typename T>
 hipError_t launch_kd_chain_tsit5_ens(const LayerConst* hlcs, int nl, const LayerConst* lcs, const T* p, int64_t P,
                                      const T* u0, int64_t B, const ChainSolveArgs& a, int64_t n_rep, hipStream_t st) {
     if (n_rep < 1 || n_rep > kTrainMaxReplicas || a.rec || a.cap != 0) return hipErrorNotSupported;
     if (!chain_tsit5_ens_supported(hlcs, nl, P, B, sizeof(T))) return hipErrorNotSupported;
-    const size_t lds = nl * sizeof(LayerConst) + (size_t)P * sizeof(T);
-    const int threads = (int)((B * kChainDim + kWave - 1) / kWave) * kWave;
-    const LayerConst& h = hlcs[0];
-#define KAN_CSOLVE_E(NORM, PATH, S)                                                                                  \
-    hipLaunchKernelGGL((kd_chain_tsit5_ens_kernel<T, NORM, PATH, S>), dim3((unsigned)n_rep), dim3(threads), lds, st, \
-                       lcs, nl, p, (int)P, u0, B, a)
-    if (h.norm == NORM_TANH_FAST && h.path == PATH_REC && chain_is_lv(hlcs, nl))
-        KAN_CSOLVE_E(NORM_TANH_FAST, PATH_REC, ChainShapeLV);
-    else if (h.norm == NORM_TANH_FAST && h.path == PATH_REC) KAN_CSOLVE_E(NORM_TANH_FAST, PATH_REC, ChainShapeAny);
-    else if (h.path == PATH_REC_CORR) KAN_CSOLVE_E(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny);
-    else if (h.path == PATH_REC) KAN_CSOLVE_E(NORM_RUNTIME, PATH_REC, ChainShapeAny);
-    else KAN_CSOLVE_E(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny);
-#undef KAN_CSOLVE_E
+    const size_t lds = chain_param_lds(kChainLimits, nl, P, sizeof(T));
+    const int threads = chain_threads(kChainLimits, B);
+    chain_ladder(hlcs, nl, [&](auto norm, auto path, auto shape) {
+        hipLaunchKernelGGL((kd_chain_tsit5_ens_kernel<T, norm(), path(), decltype(shape)>), dim3((unsigned)n_rep),
+                           dim3(threads), lds, st, lcs, nl, p, (int)P, u0, B, a);
+    });
     return hipGetLastError();
 }
 template hipError_t launch_kd_chain_tsit5_ens<double>(const LayerConst*, int, const LayerConst*, const double*, int64_t,
@@ -168,28 +154,10 @@ hipError_t launch_fk_small_tsit5_ens(const LayerConst& hlc, const PPConst& hpc, 
     const int threads = (int)B * kWave;
     const double2* t2 = reinterpret_cast<const double2*>(tables);
     const int64_t ts2 = table_stride / 2;
-#define KAN_SMALL_FWD_E(NORM, PATH, GT)                                                                              \
-    do {                                                                                                             \
-        if (threads <= 256)                                                                                          \
-            hipLaunchKernelGGL((fk_small_tsit5_ens_kernel<NORM, PATH, GT, 256>), dim3((unsigned)n_rep), dim3(threads), \
-                               lds, st, lc, p, (int)P, t2, ts2, s, u0, B, a);                                        \
-        else                                                                                                         \
-            hipLaunchKernelGGL((fk_small_tsit5_ens_kernel<NORM, PATH, GT, 1024>), dim3((unsigned)n_rep),             \
-                               dim3(threads), lds, st, lc, p, (int)P, t2, ts2, s, u0, B, a);                         \
-    } while (0)
-    // (kan_small.hip's ladder)
-    if (hlc.path == PATH_REC_CORR) {
-        if (hlc.G == 10 && hlc.norm == NORM_SOFTSIGN) KAN_SMALL_FWD_E(NORM_SOFTSIGN, PATH_REC_CORR, 10);
-        else if (hlc.G == 10) KAN_SMALL_FWD_E(NORM_TANH_FAST, PATH_REC_CORR, 10);
-        else if (hlc.norm == NORM_SOFTSIGN) KAN_SMALL_FWD_E(NORM_SOFTSIGN, PATH_REC_CORR, 5);
-        else KAN_SMALL_FWD_E(NORM_TANH_FAST, PATH_REC_CORR, 5);
-    } else {
-        if (hlc.G == 10 && hlc.norm == NORM_SOFTSIGN) KAN_SMALL_FWD_E(NORM_SOFTSIGN, PATH_REC, 10);
-        else if (hlc.G == 10) KAN_SMALL_FWD_E(NORM_TANH_FAST, PATH_REC, 10);
-        else if (hlc.norm == NORM_SOFTSIGN) KAN_SMALL_FWD_E(NORM_SOFTSIGN, PATH_REC, 5);
-        else KAN_SMALL_FWD_E(NORM_TANH_FAST, PATH_REC, 5);
-    }
-#undef KAN_SMALL_FWD_E
+    fk_small_ladder(hlc, threads, [&](auto norm, auto path, auto gt, auto maxt) {
+        hipLaunchKernelGGL((fk_small_tsit5_ens_kernel<norm(), path(), gt(), maxt()>), dim3((unsigned)n_rep),
+                           dim3(threads), lds, st, lc, p, (int)P, t2, ts2, s, u0, B, a);
+    });
     return hipGetLastError();
 }
 

@@ -138,38 +138,16 @@ bool fk_small_supported(const LayerConst& hlc, const PPConst& hpc, int Nx, int64
            (hlc.G == 10 || hlc.G == 5) && (hlc.norm == NORM_SOFTSIGN || hlc.norm == NORM_TANH_FAST);
 }
 
-#define KAN_SMALL_GO(KERNEL, ...)                                                                                   \
-    do {                                                                                                          \
-        if (hlc.path == PATH_REC_CORR) {                                                                          \
-            if (hlc.G == 10 && hlc.norm == NORM_SOFTSIGN) KERNEL(NORM_SOFTSIGN, PATH_REC_CORR, 10);               \
-            else if (hlc.G == 10) KERNEL(NORM_TANH_FAST, PATH_REC_CORR, 10);                                      \
-            else if (hlc.norm == NORM_SOFTSIGN) KERNEL(NORM_SOFTSIGN, PATH_REC_CORR, 5);                          \
-            else KERNEL(NORM_TANH_FAST, PATH_REC_CORR, 5);                                                        \
-        } else {                                                                                                  \
-            if (hlc.G == 10 && hlc.norm == NORM_SOFTSIGN) KERNEL(NORM_SOFTSIGN, PATH_REC, 10);                    \
-            else if (hlc.G == 10) KERNEL(NORM_TANH_FAST, PATH_REC, 10);                                           \
-            else if (hlc.norm == NORM_SOFTSIGN) KERNEL(NORM_SOFTSIGN, PATH_REC, 5);                               \
-            else KERNEL(NORM_TANH_FAST, PATH_REC, 5);                                                             \
-        }                                                                                                         \
-    } while (0)
-
 hipError_t launch_fk_small_tsit5(const LayerConst& hlc, const PPConst& hpc, const LayerConst* lc, const double* p,
                                  const double* tables, const FkSmallArgs& s, const double* u0, int64_t B,
                                  const ChainSolveArgs& a, hipStream_t st) {
     if (!fk_small_supported(hlc, hpc, s.Nx, B) || s.ni != hpc.ni) return hipErrorNotSupported;
     const size_t lds = sizeof(double2) * (kPPCoef / 2) * (size_t)hpc.ni;
     const int threads = (int)B * kWave;
-#define KAN_SMALL_FWD(NORM, PATH, GT)                                                                              \
-    do {                                                                                                         \
-        if (threads <= 256)                                                                                      \
-            hipLaunchKernelGGL((fk_small_tsit5_kernel<NORM, PATH, GT, 256>), dim3(1), dim3(threads), lds, st, lc, p, \
-                               (const double2*)tables, s, u0, B, a);                                             \
-        else                                                                                                     \
-            hipLaunchKernelGGL((fk_small_tsit5_kernel<NORM, PATH, GT, 1024>), dim3(1), dim3(threads), lds, st, lc, \
-                               p, (const double2*)tables, s, u0, B, a);                                          \
-    } while (0)
-    KAN_SMALL_GO(KAN_SMALL_FWD);
-#undef KAN_SMALL_FWD
+    fk_small_ladder(hlc, threads, [&](auto norm, auto path, auto gt, auto maxt) {
+        hipLaunchKernelGGL((fk_small_tsit5_kernel<norm(), path(), gt(), maxt()>), dim3(1), dim3(threads), lds, st, lc, p,
+                           (const double2*)tables, s, u0, B, a);
+    });
     return hipGetLastError();
 }
 
@@ -186,27 +164,15 @@ hipError_t launch_fk_small_adjoint(const LayerConst& hlc, const PPConst& hpc, co
     const int stage_rec = lds + rec <= 150 * 1024 ? 1 : 0;
     if (stage_rec) lds += rec;
     const int threads = (int)B * kWave;
-#define KAN_SMALL_ADJ1(NORM, PATH, GT, MAXT)                                                                       \
-    do {                                                                                                         \
-        {                                                                                                        \
-            const void* fn = reinterpret_cast<const void*>(&fk_small_adjoint_kernel<NORM, PATH, GT, MAXT>);        \
-            hipError_t e_ = ensure_dynamic_lds(fn, lds);                                                         \
-            if (e_ != hipSuccess) return e_;                                                                     \
-        }                                                                                                        \
-        hipLaunchKernelGGL((fk_small_adjoint_kernel<NORM, PATH, GT, MAXT>), dim3(1), dim3(threads), lds, st, lc, p, \
-                           (const double2*)tables, s, B, a, stage_rec);                                          \
-    } while (0)
-#define KAN_SMALL_ADJ(NORM, PATH, GT)                                                                              \
-    do {                                                                                                         \
-        if (threads <= 256) KAN_SMALL_ADJ1(NORM, PATH, GT, 256);                                                 \
-        else KAN_SMALL_ADJ1(NORM, PATH, GT, 1024);                                                               \
-    } while (0)
-    KAN_SMALL_GO(KAN_SMALL_ADJ);
-#undef KAN_SMALL_ADJ
-#undef KAN_SMALL_ADJ1
-    return hipGetLastError();
+    return fk_small_ladder(hlc, threads, [&](auto norm, auto path, auto gt, auto maxt) {
+        const void* fn = reinterpret_cast<const void*>(&fk_small_adjoint_kernel<norm(), path(), gt(), maxt()>);
+        const hipError_t e = ensure_dynamic_lds(fn, lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((fk_small_adjoint_kernel<norm(), path(), gt(), maxt()>), dim3(1), dim3(threads), lds, st, lc,
+                           p, (const double2*)tables, s, B, a, stage_rec);
+        return hipGetLastError();
+    });
 }
-#undef KAN_SMALL_GO
 
 // wide (KANODE_OPT_FSENS_WIDE): 0 = the one-entry kernel alone (Nx·B <= 64); 1 = the two-entry kernel above 64
 // entries, up to 128; 2 = the two-entry kernel for every Nx·B <= 128 (tests)
@@ -226,32 +192,14 @@ hipError_t launch_fk_small_fsens(const LayerConst& hlc, const PPConst& hpc, bool
     const bool two = wide == 2 || (int64_t)s.Nx * B > kWave;   // entries per lane
     const size_t lds = sizeof(double) * fk_small_fsens_lds_doubles(tab, hpc.ni, hlc.G, two);
     if (lds > 150 * 1024) return hipErrorNotSupported;
-#define KAN_FSENS2(NORM, GT, TAB, E)                                                                               \
-    do {                                                                                                         \
-        const void* fn = reinterpret_cast<const void*>(&fk_small_fsens_kernel<NORM, GT, TAB, E>);                \
-        hipError_t e_ = ensure_dynamic_lds(fn, lds);                                                             \
-        if (e_ != hipSuccess) return e_;                                                                         \
-        hipLaunchKernelGGL((fk_small_fsens_kernel<NORM, GT, TAB, E>), dim3(1), dim3(threads), lds, st, lc, p,      \
-                           (const double2*)tables, s, u0, B, a, s_save);                                         \
-    } while (0)
-#define KAN_FSENS1(NORM, GT, TAB)                                                                                  \
-    do {                                                                                                         \
-        if (two) KAN_FSENS2(NORM, GT, TAB, 2);                                                                   \
-        else KAN_FSENS2(NORM, GT, TAB, 1);                                                                       \
-    } while (0)
-#define KAN_FSENS(NORM, GT)                                                                                        \
-    do {                                                                                                         \
-        if (tab) KAN_FSENS1(NORM, GT, true);                                                                     \
-        else KAN_FSENS1(NORM, GT, false);                                                                        \
-    } while (0)
-    if (hlc.G == 10 && hlc.norm == NORM_SOFTSIGN) KAN_FSENS(NORM_SOFTSIGN, 10);
-    else if (hlc.G == 10) KAN_FSENS(NORM_TANH_FAST, 10);
-    else if (hlc.norm == NORM_SOFTSIGN) KAN_FSENS(NORM_SOFTSIGN, 5);
-    else KAN_FSENS(NORM_TANH_FAST, 5);
-#undef KAN_FSENS
-#undef KAN_FSENS1
-#undef KAN_FSENS2
-    return hipGetLastError();
+    return fk_fsens_ladder(hlc, tab, two, [&](auto norm, auto gt, auto tb, auto e) {
+        const void* fn = reinterpret_cast<const void*>(&fk_small_fsens_kernel<norm(), gt(), tb(), e()>);
+        const hipError_t err = ensure_dynamic_lds(fn, lds);
+        if (err != hipSuccess) return err;
+        hipLaunchKernelGGL((fk_small_fsens_kernel<norm(), gt(), tb(), e()>), dim3(1), dim3(threads), lds, st, lc, p,
+                           (const double2*)tables, s, u0, B, a, s_save);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace kan

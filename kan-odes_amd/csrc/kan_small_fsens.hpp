@@ -413,4 +413,35 @@ __device__ __forceinline__ void fk_small_fsens_body(const Math<double>& M, const
     }
 }
 
+// ---- the specialisation ladders of the small-field launchers (host) ----------------------------------------------
+// The plain solve and the adjoint of a field fk_small_supported accepts: go(norm, path, gt, maxt) with PATH_REC_CORR
+// or PATH_REC, G = 10 or 5, softsign or tanh_fast, and the launch bound 256 or 1024 that holds `threads`.
+template <class Go>
+auto fk_small_ladder(const LayerConst& hlc, int threads, Go&& go) {
+    auto by_block = [&](auto norm, auto path, auto gt) {
+        return threads <= 256 ? go(norm, path, gt, ITag<256>{}) : go(norm, path, gt, ITag<1024>{});
+    };
+    auto by_norm = [&](auto path, auto gt) {
+        return hlc.norm == NORM_SOFTSIGN ? by_block(ITag<NORM_SOFTSIGN>{}, path, gt)
+                                         : by_block(ITag<NORM_TANH_FAST>{}, path, gt);
+    };
+    auto by_g = [&](auto path) { return hlc.G == 10 ? by_norm(path, ITag<10>{}) : by_norm(path, ITag<5>{}); };
+    return hlc.path == PATH_REC_CORR ? by_g(ITag<PATH_REC_CORR>{}) : by_g(ITag<PATH_REC>{});
+}
+// The Dual solve and the training loop on it (fk_small_fsens_supported): go(norm, gt, tab, e) with G = 10 or 5,
+// softsign or tanh_fast, the tables or the reference formula, and two entries per lane or one.
+template <class Go>
+auto fk_fsens_ladder(const LayerConst& hlc, bool tab, bool two, Go&& go) {
+    auto by_e = [&](auto norm, auto gt, auto tb) {
+        return two ? go(norm, gt, tb, ITag<2>{}) : go(norm, gt, tb, ITag<1>{});
+    };
+    auto by_tab = [&](auto norm, auto gt) {
+        return tab ? by_e(norm, gt, std::true_type{}) : by_e(norm, gt, std::false_type{});
+    };
+    auto by_norm = [&](auto gt) {
+        return hlc.norm == NORM_SOFTSIGN ? by_tab(ITag<NORM_SOFTSIGN>{}, gt) : by_tab(ITag<NORM_TANH_FAST>{}, gt);
+    };
+    return hlc.G == 10 ? by_norm(ITag<10>{}) : by_norm(ITag<5>{});
+}
+
 }  // namespace kan

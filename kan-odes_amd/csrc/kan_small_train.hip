@@ -354,43 +354,23 @@ static hipError_t launch_fk_train(const LayerConst& hlc, const PPConst& hpc, boo
     const bool two = wide == 2 || (int64_t)s.Nx * B > kWave;   // entries per lane (launch_fk_small_fsens's rule)
     const size_t lds = sizeof(double) * fk_train_lds(tab, hpc.ni, hlc.G, two, (int64_t)s.Nx * B, a.n_save_test).total;
     if (lds > 150 * 1024 || (two && !a.rec)) return hipErrorNotSupported;
-#define KAN_FTRAIN3(NORM, GT, TAB, E, TEST)                                                                        \
-    do {                                                                                                         \
-        const void* fn = args ? reinterpret_cast<const void*>(&fk_small_train_ens_kernel<NORM, GT, TAB, E, TEST>) \
-                              : reinterpret_cast<const void*>(&fk_small_train_kernel<NORM, GT, TAB, E, TEST>);   \
-        hipError_t e_ = ensure_dynamic_lds(fn, lds);                                                             \
-        if (e_ != hipSuccess) return e_;                                                                         \
-        if (args)                                                                                                \
-            hipLaunchKernelGGL((fk_small_train_ens_kernel<NORM, GT, TAB, E, TEST>), dim3((unsigned)n_rep),       \
-                               dim3(threads), lds, st, lc, pc, s, B, args);                                      \
-        else                                                                                                     \
-            hipLaunchKernelGGL((fk_small_train_kernel<NORM, GT, TAB, E, TEST>), dim3(1), dim3(threads), lds, st, lc, pc, \
-                               s, B, a);                                                                         \
-    } while (0)
-#define KAN_FTRAIN2(NORM, GT, TAB, E)                                                                              \
-    do {                                                                                                         \
-        if (TAB && with_test) KAN_FTRAIN3(NORM, GT, TAB, E, TAB);                                                \
-        else KAN_FTRAIN3(NORM, GT, TAB, E, false);                                                               \
-    } while (0)
-#define KAN_FTRAIN1(NORM, GT, TAB)                                                                                 \
-    do {                                                                                                         \
-        if (two) KAN_FTRAIN2(NORM, GT, TAB, 2);                                                                  \
-        else KAN_FTRAIN2(NORM, GT, TAB, 1);                                                                      \
-    } while (0)
-#define KAN_FTRAIN(NORM, GT)                                                                                       \
-    do {                                                                                                         \
-        if (tab) KAN_FTRAIN1(NORM, GT, true);                                                                    \
-        else KAN_FTRAIN1(NORM, GT, false);                                                                       \
-    } while (0)
-    if (hlc.G == 10 && hlc.norm == NORM_SOFTSIGN) KAN_FTRAIN(NORM_SOFTSIGN, 10);
-    else if (hlc.G == 10) KAN_FTRAIN(NORM_TANH_FAST, 10);
-    else if (hlc.norm == NORM_SOFTSIGN) KAN_FTRAIN(NORM_SOFTSIGN, 5);
-    else KAN_FTRAIN(NORM_TANH_FAST, 5);
-#undef KAN_FTRAIN
-#undef KAN_FTRAIN1
-#undef KAN_FTRAIN2
-#undef KAN_FTRAIN3
-    return hipGetLastError();
+    // test: the kernel holds the logged-loss solve (with the tables only: fk_small_train_supported)
+    auto go = [&](auto norm, auto gt, auto tb, auto e, auto test) {
+        const void* fn = args ? reinterpret_cast<const void*>(&fk_small_train_ens_kernel<norm(), gt(), tb(), e(), test()>)
+                              : reinterpret_cast<const void*>(&fk_small_train_kernel<norm(), gt(), tb(), e(), test()>);
+        const hipError_t err = ensure_dynamic_lds(fn, lds);
+        if (err != hipSuccess) return err;
+        if (args)
+            hipLaunchKernelGGL((fk_small_train_ens_kernel<norm(), gt(), tb(), e(), test()>), dim3((unsigned)n_rep),
+                               dim3(threads), lds, st, lc, pc, s, B, args);
+        else
+            hipLaunchKernelGGL((fk_small_train_kernel<norm(), gt(), tb(), e(), test()>), dim3(1), dim3(threads), lds, st,
+                               lc, pc, s, B, a);
+        return hipGetLastError();
+    };
+    return fk_fsens_ladder(hlc, tab, two, [&](auto norm, auto gt, auto tb, auto e) {
+        return tb() && with_test ? go(norm, gt, tb, e, tb) : go(norm, gt, tb, e, std::false_type{});
+    });
 }
 
 hipError_t launch_fk_small_train(const LayerConst& hlc, const PPConst& hpc, bool tab, const LayerConst* lc,

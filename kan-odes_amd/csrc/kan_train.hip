@@ -49,20 +49,16 @@ kd_chain_train_lvsp_ens_kernel(const LayerConst* __restrict__ lcs, const ChainTr
 
 bool chain_train_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B, size_t esize, bool wide) {
     // (one path specialisation for both layers: launch_kd_chain_tsit5's condition, whose arithmetic the forward is)
-    return KAN_LV_SP && esize == sizeof(double) && P == kLvP && chain_is_lv_wave(hlcs, nl, B, wide) &&
+    return KAN_LV_SP && esize == sizeof(double) && P == kLvP && chain_is_lv_wave(kChainLimits, hlcs, nl, B, wide) &&
            hlcs[0].path == hlcs[1].path;
 }
 
+// the stage-parallel adjoint's LDS at cap steps, with the saveat times and rows of both problems beside it
 size_t chain_train_lds(int64_t cap, int64_t n_save, int64_t n_save_test, int* stage_rec) {
-    constexpr size_t kBudget = 140 * 1024;   // launch_kd_chain_adjoint's, with cap in place of nsteps
-    const size_t jst = sizeof(double) * 8 * LvWaveShape::I * (kLvP + LvWaveShape::I);
-    const size_t rec = sizeof(double) * ((size_t)cap * 7 + 1) * LvWaveShape::I;
-    size_t lsp = 2 * sizeof(LayerConst) +
-                 sizeof(double) * (kLvP + 2 * (size_t)cap + (size_t)(1 + LvWaveShape::I) * (n_save + n_save_test));
-    const int sr = lsp + rec + jst <= kBudget ? 1 : 0;
-    if (sr) lsp += rec;
+    int sr = 0;
+    const size_t lds = lvsp_lds(kChainLimits, cap, (size_t)(1 + LvWaveShape::I) * (n_save + n_save_test), &sr);
     if (stage_rec) *stage_rec = sr;
-    return lsp + jst <= kBudget ? lsp : 0;
+    return lds;
 }
 
 // args == nullptr: the single-replica kernel on `a`; else the ensemble kernel, one workgroup per struct of the device
@@ -78,7 +74,8 @@ static hipError_t launch_chain_train(const LayerConst* hlcs, int nl, const Layer
     if (lds == 0 || sr != a.stage_rec || (!sr && !a.rec)) return hipErrorNotSupported;
     const LayerConst& h = hlcs[0];
     const bool tf = h.norm == NORM_TANH_FAST;
-    // the forward's specialisation: launch_kd_chain_tsit5's choice for this handle
+    // the forward's specialisation is the handle's rung of chain_ladder, paired here with the adjoint's normalizer:
+    // only these six combinations exist, so the ladder stays written out
 #define KAN_TRAIN_GO(NORM, FN, PATH, FS)                                                                            \
     do {                                                                                                            \
         const void* fn = args ? reinterpret_cast<const void*>(&kd_chain_train_lvsp_ens_kernel<NORM, FN, PATH, FS>)  \

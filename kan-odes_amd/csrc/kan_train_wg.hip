@@ -253,8 +253,8 @@ __device__ __noinline__ void wg_adam(const ChainTrainArgs& a, const TrainWgPtrs&
     }
 }
 
-// FN, PATH, FS: the forward's ChainModel specialisation (launch_kd_chain_tsit5's choice for the handle), which is
-// the ChainModel adjoint's too (launch_kd_chain_adjoint's ladder is the same); ADJ, WN: the adjoint's model
+// FN, PATH, FS: the forward's ChainModel specialisation (the handle's rung of chain_ladder), which is the ChainModel
+// adjoint's too; ADJ, WN: the adjoint's model
 template <int FN, int PATH, class FS, int ADJ, int WN>
 __global__ void __launch_bounds__(kChainBlock)
 kd_chain_train_wg_kernel(const LayerConst* __restrict__ lcs, int nl, int P, ChainTrainArgs a) {
@@ -353,37 +353,14 @@ kd_chain_train_wg_kernel(const LayerConst* __restrict__ lcs, int nl, int P, Chai
     }
 }
 
-// the conditions of launch_kd_chain_tsit5 and of launch_kd_chain_adjoint's two one-workgroup models, with `cap` in
-// place of the step count (what holds at cap holds at every count the loop can reach)
-static bool train_wg_small_layers(const LayerConst* hlcs, int nl) {
-    for (int l = 0; l < nl; ++l) {
-        const LayerConst& h = hlcs[l];
-        if (h.I > kChainDim || h.O > kChainDim || h.path != hlcs[0].path || h.norm != hlcs[0].norm) return false;
-        if (l > 0 && h.I != hlcs[l - 1].O) return false;
-    }
-    return true;
-}
-static int train_wg_model(const LayerConst* hlcs, int nl, int64_t P, int64_t B, bool wide, int64_t cap, int* stage_rec) {
-    if (stage_rec) *stage_rec = 0;
-    if (nl < 1 || nl > kChainMaxLayers || B < 1 || B > kChainSolveMaxBatch || I_ne_O(hlcs, nl) || cap < 1 ||
-        cap > kChainAdjointMaxSteps || !train_wg_small_layers(hlcs, nl) ||
-        nl * sizeof(LayerConst) + (size_t)P * sizeof(double) > 48 * 1024 || (nl * sizeof(LayerConst)) % 8)
-        return kWgNone;
-    if (wide && B == 1 && nl == 2 && hlcs[0].use_base && hlcs[1].use_base && hlcs[0].norm == hlcs[1].norm &&
-        hlcs[1].I == hlcs[0].O && wide_fits(WideShape{hlcs[0].I, hlcs[0].O, hlcs[1].O, hlcs[0].G, hlcs[1].G}) &&
-        (hlcs[0].norm == NORM_TANH_FAST || hlcs[0].norm == NORM_SOFTSIGN)) {
-        const size_t pre = 2 * sizeof(LayerConst) + sizeof(double) * ((size_t)P * 10 + WideModel<double, NORM_SOFTSIGN>::kEnd);
-        const size_t lds = pre + 2 * sizeof(double) * cap;
-        const size_t rec = sizeof(double) * ((size_t)cap * 7 + 1) * hlcs[0].I;
-        if (lds <= 60 * 1024) {
-            if (stage_rec) *stage_rec = lds + rec <= 60 * 1024 ? 1 : 0;
-            return kWgWide;
-        }
-    }
-    const int threads = (int)((B * kChainDim + kWave - 1) / kWave) * kWave;
-    const int NG = threads / kChainDim;
-    const size_t lds = nl * sizeof(LayerConst) + (size_t)P * sizeof(double) * (1 + NG + 9) + 2 * sizeof(double) * cap + 16;
-    return lds <= 60 * 1024 ? kWgChain : kWgNone;
+// The adjoint's model, block and staging: where the forward fits the one-workgroup solve (at any step count: it keeps
+// no dense output of its own), the plan of the one-workgroup adjoint at `cap` steps.  Its WideModel or ChainModel:
+// this kernel has no LvWaveModel (chain_train_wg_supported leaves that shape to kd_chain_train_lvsp_kernel).
+static ChainAdjPlan train_wg_plan(const LayerConst* hlcs, int nl, int64_t P, int64_t B, bool wide, int64_t cap) {
+    if (!chain_small_layers(kChainLimits, hlcs, nl, kChainLimits.vjp_layers) ||
+        !chain_params_fit(kChainLimits, nl, P, sizeof(double)) || (nl * sizeof(LayerConst)) % 8)
+        return ChainAdjPlan{kAdjNone, 0, 0, 0};
+    return chain_adjoint_plan(kChainLimits, hlcs, nl, P, B, wide, cap, sizeof(double), false);
 }
 
 size_t chain_train_wg_rec_elems(int64_t n, int64_t cap, int64_t n_save, int64_t n_save_test) {
@@ -393,14 +370,13 @@ size_t chain_train_wg_rec_elems(int64_t n, int64_t cap, int64_t n_save, int64_t 
 size_t chain_train_wg_lds(const LayerConst* hlcs, int nl, int64_t P, int64_t B, bool wide, int64_t cap, int64_t n_save,
                           int64_t n_save_test, int* dl_lds, int* stage_rec) {
     constexpr size_t kBudget = 140 * 1024 - 4096;   // chain_train_lds's, less the kernel's static LDS (the exp table)
-    int sr = 0;
-    const int model = train_wg_model(hlcs, nl, P, B, wide, cap, &sr);
+    const ChainAdjPlan plan = train_wg_plan(hlcs, nl, P, B, wide, cap);
+    int sr = plan.stage_rec;
     if (dl_lds) *dl_lds = 0;
     if (stage_rec) *stage_rec = 0;
-    if (model == kWgNone || n_save < 0 || n_save_test < 0) return 0;
+    if (plan.model == kAdjNone || n_save < 0 || n_save_test < 0) return 0;
     const int64_t n = (int64_t)hlcs[0].I * B;
-    const int threads = model == kWgWide ? kChainBlock : (int)((B * kChainDim + kWave - 1) / kWave) * kWave;
-    const int64_t work = model == kWgWide ? (int64_t)WideModel<double, NORM_SOFTSIGN>::kEnd : (int64_t)(threads / kChainDim) * P;
+    const int64_t work = plan.model == kAdjWide ? (int64_t)kChainLimits.wide_end : (int64_t)(plan.threads / kChainDim) * P;
     const size_t lc = nl * sizeof(LayerConst);
     auto bytes = [&](int dl, int st) {
         return lc + sizeof(double) * train_wg_carve(P, work, cap, n_save, n_save_test, n, dl, st).total;
@@ -414,7 +390,7 @@ size_t chain_train_wg_lds(const LayerConst* hlcs, int nl, int64_t P, int64_t B, 
 }
 
 bool chain_train_wg_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t B, size_t esize, bool wide) {
-    if (esize != sizeof(double) || nl < 1 || chain_is_lv_wave(hlcs, nl, B, wide)) return false;
+    if (esize != sizeof(double) || nl < 1 || chain_is_lv_wave(kChainLimits, hlcs, nl, B, wide)) return false;
     return chain_train_wg_lds(hlcs, nl, P, B, wide, 1, 1, 0, nullptr, nullptr) != 0;
 }
 
@@ -426,8 +402,8 @@ hipError_t launch_kd_chain_train_wg(const LayerConst* hlcs, int nl, const LayerC
     int dl = 0, sr = 0;
     const size_t lds = chain_train_wg_lds(hlcs, nl, P, B, wide, a.cap, a.n_save, a.n_save_test, &dl, &sr);
     if (lds == 0 || dl != a.dl_lds || sr != a.stage_rec) return hipErrorNotSupported;
-    const int model = train_wg_model(hlcs, nl, P, B, wide, a.cap, nullptr);
-    const int threads = model == kWgWide ? kChainBlock : (int)((B * kChainDim + kWave - 1) / kWave) * kWave;
+    const ChainAdjPlan plan = train_wg_plan(hlcs, nl, P, B, wide, a.cap);
+    const int threads = plan.threads;
     const LayerConst& h = hlcs[0];
 #define KAN_TWG_GO(FN, PATH, FS, ADJ, WN)                                                                            \
     do {                                                                                                            \
@@ -437,26 +413,23 @@ hipError_t launch_kd_chain_train_wg(const LayerConst* hlcs, int nl, const LayerC
         hipLaunchKernelGGL((kd_chain_train_wg_kernel<FN, PATH, FS, ADJ, WN>), dim3(1), dim3(threads), lds, st, lcs, \
                            nl, (int)P, a);                                                                          \
     } while (0)
-    // the forward's specialisation is launch_kd_chain_tsit5's ladder; only the combinations a handle reaches exist
-    // (a [2,10,2] G = 5 chain on the exact recurrence under WideModel is the LV-wave shape: not this kernel's)
+    // the forward's specialisation is the ladder's rung.  Under WideModel the rung is paired with the adjoint's
+    // normalizer and only the six combinations a handle reaches exist (a [2,10,2] G = 5 chain on the exact
+    // recurrence under WideModel is the LV-wave shape: not this kernel's), so that half stays written out
     const bool tf = h.norm == NORM_TANH_FAST;
-    if (model == kWgWide) {
+    if (plan.model == kAdjWide) {
         if (tf && h.path == PATH_REC) KAN_TWG_GO(NORM_TANH_FAST, PATH_REC, ChainShapeAny, kWgWide, NORM_TANH_FAST);
         else if (tf && h.path == PATH_REC_CORR) KAN_TWG_GO(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny, kWgWide, NORM_TANH_FAST);
         else if (tf) KAN_TWG_GO(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny, kWgWide, NORM_TANH_FAST);
         else if (h.path == PATH_REC_CORR) KAN_TWG_GO(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny, kWgWide, NORM_SOFTSIGN);
         else if (h.path == PATH_REC) KAN_TWG_GO(NORM_RUNTIME, PATH_REC, ChainShapeAny, kWgWide, NORM_SOFTSIGN);
         else KAN_TWG_GO(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny, kWgWide, NORM_SOFTSIGN);
-    } else if (tf && h.path == PATH_REC && chain_is_lv(hlcs, nl)) {
-        KAN_TWG_GO(NORM_TANH_FAST, PATH_REC, ChainShapeLV, kWgChain, NORM_RUNTIME);
-    } else if (tf && h.path == PATH_REC) {
-        KAN_TWG_GO(NORM_TANH_FAST, PATH_REC, ChainShapeAny, kWgChain, NORM_RUNTIME);
-    } else if (h.path == PATH_REC_CORR) {
-        KAN_TWG_GO(NORM_RUNTIME, PATH_REC_CORR, ChainShapeAny, kWgChain, NORM_RUNTIME);
-    } else if (h.path == PATH_REC) {
-        KAN_TWG_GO(NORM_RUNTIME, PATH_REC, ChainShapeAny, kWgChain, NORM_RUNTIME);
     } else {
-        KAN_TWG_GO(NORM_RUNTIME, PATH_DIRECT, ChainShapeAny, kWgChain, NORM_RUNTIME);
+        const hipError_t e = chain_ladder(hlcs, nl, [&](auto norm, auto path, auto shape) {
+            KAN_TWG_GO(norm(), path(), decltype(shape), kWgChain, NORM_RUNTIME);
+            return hipSuccess;
+        });
+        if (e != hipSuccess) return e;
     }
 #undef KAN_TWG_GO
     return hipGetLastError();
