@@ -1,0 +1,193 @@
+// kanode_train_launch.cpp — the launches of the device-resident training loops (kanode_train.cpp calls them through
+// kanode_internal.hpp): the handle's training buffer, the capacity of one forward solve, and the single-replica or
+// ensemble launch of the chain loops (kan_train.hip, kan_train_wg.hip) and the Fisher-KPP loop (kan_small_train.hip).
+#include "kanode.h"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "kanode_handle.hpp"
+
+// the Lotka-Volterra loop's shapes (kd_chain_train_lvsp_kernel): whatever KANODE_OPT_TRAIN_ANY_CHAIN says
+static bool chain_train_lv_ok(const kanode_handle* h, int64_t batch) {
+    return h->spec.rhs_kind == KANODE_RHS_CHAIN && kanode_internal_chain_tsit5_ok(h, batch) &&
+           kan::chain_train_supported(h->hlc, h->n_layers, h->P, batch, h->esize, h->opt.chain_wide);
+}
+// with the option on: every other small fp64 chain (kd_chain_train_wg_kernel)
+static bool chain_train_wg_ok(const kanode_handle* h, int64_t batch) {
+    return h->opt.train_any_chain && h->spec.dtype == KANODE_F64 && h->spec.rhs_kind == KANODE_RHS_CHAIN &&
+           kanode_internal_chain_tsit5_ok(h, batch) &&
+           kan::chain_train_wg_supported(h->hlc, h->n_layers, h->P, batch, h->esize, h->opt.chain_wide);
+}
+bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch) {
+    return chain_train_lv_ok(h, batch) || chain_train_wg_ok(h, batch);
+}
+// The handle's training-loop buffer: result words | (the loop's private block) | meta at off_meta (an ensemble
+// launch: kan_ensemble.hpp's layout, the per-replica blocks and structs before the one meta), grown on
+// demand; meta is uploaded only when it differs from the last call's bytes.
+static kanode_status train_buf_stage(kanode_handle* h, size_t off_meta, const std::vector<char>& meta, hipStream_t st,
+                                     char*& base) {
+    const size_t need = off_meta + meta.size() + 64;
+    if (h->train_buf.bytes() < need) {
+        HIP_TRY(h, hipStreamSynchronize(st));
+        h->train_meta.clear();   // (its device copy goes)
+        h->train_meta_off = 0;
+        HIP_TRY(h, h->train_buf.reserve(need));
+    }
+    base = (char*)h->train_buf.ptr();
+    if (h->train_meta != meta || h->train_meta_off != off_meta) {
+        // (the earlier calls synchronised, so nothing on the device still reads the old bytes)
+        HIP_TRY(h, hipMemcpy(base + off_meta, meta.data(), meta.size(), hipMemcpyHostToDevice));
+        h->train_meta = meta;
+        h->train_meta_off = off_meta;
+    }
+    return KANODE_OK;
+}
+// The launch of either loop once a's pointers into the single-replica buffer layout (status words at base, the
+// private block at off_rec) are set, or, with ens, the ensemble launch: the buffer is laid out for ens->R replicas
+// (kan_ensemble.hpp), the per-replica structs are formed from *a and uploaded with the meta, and launch(a, args, R)
+// starts one workgroup per struct.  rec_bytes: a replica's private block (0: none).  Synchronises; res [R][2] =
+// iterations done, stop reason of every replica.
+template <class Launch>
+static kanode_status train_launch(kanode_handle* h, const char* what, kan::ChainTrainArgs* a,
+                                  const kan::EnsembleReplicas* ens, size_t rec_bytes, const std::vector<char>& meta,
+                                  int64_t* res, hipStream_t st, Launch&& launch) {
+    const int64_t R = ens ? ens->R : 1;
+    kan::EnsembleLayout L{};
+    if (ens) L = kan::ensemble_layout(R, rec_bytes, sizeof(kan::ChainTrainArgs));
+    else {   // (the single-replica layout: result words | private block | meta)
+        L.off_rec = 64;
+        L.rec_stride = rec_bytes;
+        L.off_args = L.off_meta = L.off_rec + rec_bytes;
+    }
+    char* base = nullptr;
+    if (const kanode_status r = train_buf_stage(h, L.off_meta, meta, st, base); r != KANODE_OK) return r;
+    const double* md = (const double*)(base + L.off_meta);
+    a->saveat = md;
+    a->saveat_test = md + a->n_save;
+    a->stops = md + a->n_save + a->n_save_test;
+    a->joff = (const int32_t*)(a->stops + a->nstops);
+    a->jrows = a->joff + a->nstops + 2;
+    a->rec = rec_bytes ? (double*)(base + L.off_rec) : nullptr;
+    a->out = (int64_t*)base;
+    const kan::ChainTrainArgs* dargs = nullptr;
+    if (ens) {
+        std::vector<kan::ChainTrainArgs> args((size_t)R);
+        kan::ensemble_fill_args(*a, *ens, L, base, args.data());
+        // (the earlier calls synchronised, so nothing on the device still reads the old structs)
+        HIP_TRY(h, hipMemcpy(base + L.off_args, args.data(), args.size() * sizeof(kan::ChainTrainArgs),
+                             hipMemcpyHostToDevice));
+        dargs = (const kan::ChainTrainArgs*)(base + L.off_args);
+    }
+    const hipError_t e = launch(*a, dargs, R);
+    if (e == hipErrorNotSupported)
+        return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (shape or saveat lists not covered "
+                                                                   "by the one-workgroup training kernel)");
+    if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(res, base, (size_t)R * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return KANODE_OK;
+}
+// kanode_train_tsit5 on a chain that is not the Lotka-Volterra loop's (KANODE_OPT_TRAIN_ANY_CHAIN): the capacity by
+// the same rules (the option, a fixed-step solve's own count, else the most steps that leave u_save / dl in LDS, at
+// least 64, else kChainAdjointMaxSteps or what fits), the private block sized for it
+static kanode_status chain_train_wg(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
+                                    const std::vector<char>& meta, int64_t* res, hipStream_t st) {
+    const char* what = "kanode_train_tsit5";
+    const bool wide = h->opt.chain_wide;
+    auto lds = [&](int64_t cap, int* dl, int* sr) {
+        return kan::chain_train_wg_lds(h->hlc, h->n_layers, h->P, batch, wide, cap, a->n_save, a->n_save_test, dl, sr);
+    };
+    int64_t cap = std::min<int64_t>(h->opt.fused_solve_cap, kan::kChainAdjointMaxSteps);
+    if (cap < 1) {
+        auto largest = [&](bool want_dl) {   // the largest cap that fits (want_dl: with u_save / dl in LDS), 0: none
+            return largest_fitting(kan::kChainAdjointMaxSteps, [&](int64_t c) {
+                int dl = 0;
+                return lds(c, &dl, nullptr) && (dl || !want_dl);
+            });
+        };
+        cap = largest(true);
+        if (cap < 64) cap = largest(false);
+    }
+    if (!a->adaptive && h->opt.fused_solve_cap < 1)
+        cap = std::max<int64_t>(kanode_fixed_step_count(a->t0, a->tf, a->dt, kan::kChainAdjointMaxSteps), 1);
+    int dl = 0, sr = 0;
+    if (cap < 1 || !lds(cap, &dl, &sr))
+        return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (the problem does not fit one workgroup's LDS)");
+    a->cap = cap;
+    a->stage_rec = sr;
+    a->dl_lds = dl;
+    a->B = batch;
+    a->N = h->n_in;
+    const size_t rec_bytes =
+        sizeof(double) * kan::chain_train_wg_rec_elems(a->N * batch, cap, a->n_save, a->n_save_test);
+    return train_launch(h, what, a, nullptr, (rec_bytes + 63) & ~(size_t)63, meta, res, st,
+                        [&](const kan::ChainTrainArgs& a0, const kan::ChainTrainArgs*, int64_t) {
+                            return kan::launch_kd_chain_train_wg(h->hlc, h->n_layers, h->dlc(), h->P, batch, wide, a0, st);
+                        });
+}
+kanode_status kanode_internal_chain_train(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
+                                          const kan::EnsembleReplicas* ens, const std::vector<char>& meta, int64_t* res,
+                                          void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const char* what = ens ? "kanode_train_ensemble_tsit5" : "kanode_train_tsit5";
+    if (!chain_train_lv_ok(h, batch)) {
+        if (ens || !chain_train_wg_ok(h, batch))   // (an ensemble of general chains is out of scope: nothing launched)
+            return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (the ensemble entry covers one "
+                                                                       "Lotka-Volterra trajectory per replica)");
+        return chain_train_wg(h, batch, a, meta, res, st);
+    }
+    // the dense-output capacity of one forward solve: KANODE_OPT_FUSED_SOLVE_CAP, else the most steps whose dense
+    // output still fits in LDS next to the rest (at least 64: a smaller block stays in global memory instead)
+    int64_t cap = std::min<int64_t>(h->opt.fused_solve_cap, kan::kChainAdjointMaxSteps);
+    if (cap < 1) {
+        const int64_t staged = largest_fitting(kan::kChainAdjointMaxSteps, [&](int64_t c) {   // the largest staged cap
+            int sr = 0;
+            return kan::chain_train_lds(c, a->n_save, a->n_save_test, &sr) && sr;
+        });
+        cap = staged >= 64 ? staged : kan::kChainAdjointMaxSteps;
+    }
+    if (!a->adaptive && h->opt.fused_solve_cap < 1)   // fixed steps: exactly the steps of the solve (solve_fused_t's count)
+        cap = std::max<int64_t>(kanode_fixed_step_count(a->t0, a->tf, a->dt, kan::kChainAdjointMaxSteps), 1);
+    int stage_rec = 0;
+    if (!kan::chain_train_lds(cap, a->n_save, a->n_save_test, &stage_rec))
+        return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (saveat lists too long for one workgroup's LDS)");
+    a->cap = cap;
+    a->stage_rec = stage_rec;
+    // the global dense-output block: the single-replica buffer always holds the largest one (kChainAdjointMaxSteps,
+    // not this launch's cap); every replica of an ensemble gets its own, of this launch's capacity, and none where
+    // the dense output is staged in LDS
+    const size_t rec_bytes = sizeof(double) * ((size_t)(ens ? cap : kan::kChainAdjointMaxSteps) * 7 * 2 + 2);
+    return train_launch(h, what, a, ens, ens && stage_rec ? 0 : rec_bytes, meta, res, st,
+                        [&](const kan::ChainTrainArgs& a0, const kan::ChainTrainArgs* dargs, int64_t R) {
+                            return dargs ? kan::launch_kd_chain_train_ensemble(h->hlc, h->n_layers, h->dlc(), h->P, a0,
+                                                                               dargs, R, st)
+                                         : kan::launch_kd_chain_train(h->hlc, h->n_layers, h->dlc(), h->P, a0, st);
+                        });
+}
+
+bool kanode_internal_fk_train_ok(const kanode_handle* h, int64_t batch, bool with_test) {
+    if (!kanode_internal_fsens_ok(h, batch) || (with_test && !fk_small_ok(h, batch))) return false;
+    return kan::fk_small_train_supported(h->hlc[0], h->hpc, h->opt.pp_on && h->hpc.enabled, (int)h->spec.nx, batch,
+                                         h->opt.fsens_wide, with_test);
+}
+kanode_status kanode_internal_fk_train(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
+                                       const kan::EnsembleReplicas* ens, const std::vector<char>& meta, int64_t* res,
+                                       void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const char* what = ens ? "kanode_train_forward_ensemble_tsit5" : "kanode_train_forward_tsit5";
+    // the accumulators of the two-entries-per-lane kernel (ChainTrainArgs::rec; launch_fk_small_fsens's rule): every
+    // replica of an ensemble has its own block, and none where the kernel keeps them in LDS
+    const bool two = h->opt.fsens_wide == 2 || h->spec.nx * batch > 64;
+    const size_t rec_bytes = sizeof(double) * (size_t)kan::kFsensMaxWaves * 2 * 64;
+    const bool tab = h->opt.pp_on && h->hpc.enabled;
+    return train_launch(h, what, a, ens, ens && !two ? 0 : rec_bytes, meta, res, st,
+                        [&](const kan::ChainTrainArgs& a0, const kan::ChainTrainArgs* dargs, int64_t R) {
+                            return dargs ? kan::launch_fk_small_train_ensemble(h->hlc[0], h->hpc, tab, h->dlc(), h->dpc(),
+                                                                               fk_small_args(h), batch, a0, dargs, R,
+                                                                               h->opt.fsens_wide, st)
+                                         : kan::launch_fk_small_train(h->hlc[0], h->hpc, tab, h->dlc(), h->dpc(),
+                                                                      fk_small_args(h), batch, a0, h->opt.fsens_wide, st);
+                        });
+}

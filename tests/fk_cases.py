@@ -25,14 +25,14 @@ from oracle import kanode_np as N
 from oracle import oracle as O
 
 DIRECT, REC, REC_CORR = "direct", "rec", "rec_corr"
-K_BLOCK, K_GRID_CAP, K_SLAB_BLOCKS, K_MAX_GRID = 256, 4096, 4096, 32      # kan_common.hpp, kanode_abi.cpp
+K_BLOCK, K_GRID_CAP, K_SLAB_BLOCKS, K_MAX_GRID = 256, 4096, 4096, 32      # kan_common.hpp, kanode_options.hpp
 NORM_RANGE = {"tanh_fast": (-1.0, 1.0), "tanh": (-1.0, 1.0), "softsign": (-1.0, 1.0), "sigmoid": (0.0, 1.0),
               "sigmoid_fast": (0.0, 1.0)}                               # (identity: unbounded)
 
 
 # ---- the classification, restated -------------------------------------------------------------------------------
 def layer_consts(spec):
-    """make_layer_const's recurrence constants in float64 (kanode_abi.cpp:162-222): s, gs, δ, τ_c, Δ_j, e_j, K_j."""
+    """make_layer_const's recurrence constants in float64 (kanode_abi.cpp:43-105): s, gs, δ, τ_c, Δ_j, e_j, K_j."""
     G = spec.grid_len
     grid = N.knots(G, *spec.grid_lims)
     den = N.default_denominator(G) if spec.denominator is None else np.float32(spec.denominator)

@@ -47,7 +47,7 @@ COL, WIDE_IN, WIDE_OUT = "column", "wide-in", "wide-out"
 
 
 def kernel_class(I, O_, G, use_base, esize):
-    """The class kanode_create gives a layer (kanode_abi.cpp:926-940), restated: column when O <= 16, the
+    """The class kanode_create gives a layer (kanode_abi.cpp:209-223), restated: column when O <= 16, the
     (G·I + O + I)·65 staging fits 150 KiB and P <= 64·32; else wide-in when O <= 16 (kWideOMax); else wide-out when
     (G·I + I)·8 (kWideKT) elements fit 150 KiB; else None (refused).  This restatement can drift from the C++:
     the records state their classes by hand and test_layer_cases_cpu.py holds them against it, and the GPU

@@ -1,5 +1,5 @@
 """The wide-layer and mixed-class chain kernels against the fp64 C oracle, over the case table of
-tests/layer_cases.py: every kernel class and class pair kanode_create can form (kanode_abi.cpp:926-940), the three
+tests/layer_cases.py: every kernel class and class pair kanode_create can form (kanode_abi.cpp:209-223), the three
 load-slot instantiations of the wide-in forward, both dtypes, and the normalizer / basis / base-activation variants
 the ABI accepts.  The pass criterion is gpu_util.assert_close at the project's two RTOL values, under three scales
 of layer_cases.py: the single-layer scale for every layer call against the oracle at exact inputs (tight); the chain
@@ -96,7 +96,7 @@ def test_rhs_and_vjp_match_the_oracle(cid):
         _, dp2 = hd.vjp(x.pt, x.ut, x.lt, want_lamJ=False)
         if _chain_kernel_possible(x.c):
             # an all-column chain with N_in == N_out takes the one-launch chain kernel only when λᵀJ is asked
-            # for (vjp_t, kanode_abi.cpp:462-474); the dp-only call runs layer by layer, in another summation order
+            # for (vjp_t, kanode_eval.cpp:259-266); the dp-only call runs layer by layer, in another summation order
             assert_close(dp2, _f64(dp0), x.ps, x.rtol, "pbar (dp only, all-column chain)")
         else:
             assert torch.equal(dp2, dp0)
