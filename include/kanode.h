@@ -223,6 +223,11 @@ kanode_status kanode_reserve(kanode_handle* h, int64_t max_batch);
  *     torch-summed one in the last bits, which is why the coverage is opt-in).  The Lotka-Volterra shape runs its
  *     own kernel whatever the option says, with the same bits.  kanode_train_supported follows the option; the
  *     ensemble entry does not (it stays the Lotka-Volterra shape's).  Any value other than 0 / 1 is INVALID_ARG.
+ *   KANODE_OPT_LAST_EVAL (read-only): the launcher that served the handle's last evaluation call, a
+ *     kanode_eval_path value.  Set by kanode_rhs, kanode_vjp, kanode_rhs_stage, kanode_vjp_stage (and their *_host
+ *     forms), by the single-layer entry points (KANODE_EVAL_PER_LAYER) and, inside the integrator, by every stage
+ *     and by each one-launch small-chain step.  A launcher that declines a shape hands the call to the next one
+ *     without an error; this option says which one ran.  One integer store on the host per call.
  * Options are read when a call is issued (never from the environment).  kanode_get_option
  * returns the current value, or -1 for an unknown option. */
 typedef enum {
@@ -246,7 +251,8 @@ typedef enum {
     KANODE_OPT_RECORD_ADJOINT_STEPS = 18,
     KANODE_OPT_FK_DEVICE_LOOP = 19,
     KANODE_OPT_FSENS_WIDE = 20,
-    KANODE_OPT_TRAIN_ANY_CHAIN = 21
+    KANODE_OPT_TRAIN_ANY_CHAIN = 21,
+    KANODE_OPT_LAST_EVAL = 22
 } kanode_option;
 typedef enum {
     KANODE_ADJ_NONE = 0,            /* no adjoint on this handle yet */
@@ -255,6 +261,16 @@ typedef enum {
     KANODE_ADJ_PAIR_PERSIST = 3,    /* a surrogate pair's whole adjoint in one launch (kd_pair_adjoint_kernel) */
     KANODE_ADJ_PAIR_FALLBACK = 4    /* that launch timed out on an exchange; re-run on the host loop */
 } kanode_adjoint_path;
+typedef enum {
+    KANODE_EVAL_NONE = 0,             /* no evaluation on this handle yet */
+    KANODE_EVAL_CHAIN_KERNEL = 1,     /* a small chain in one launch (kd_chain_col_kernel / kd_chain_vjp_stage_kernel) */
+    KANODE_EVAL_CHAIN_STEP = 2,       /* a small chain's whole Tsit5 step in one launch (kd_chain_step_kernel) */
+    KANODE_EVAL_CHAIN_ADJ_STEP = 3,   /* ... its whole adjoint step (kd_chain_vjp_step_kernel) */
+    KANODE_EVAL_PER_LAYER = 4,        /* one launch (or more) per layer */
+    KANODE_EVAL_PAIR = 5,             /* the surrogate pair's launches (wide-in feeding wide-out) */
+    KANODE_EVAL_FK_TABLE = 6,         /* the Fisher-KPP table kernels (kan_pp.hip) */
+    KANODE_EVAL_FK_POINT = 7          /* the Fisher-KPP per-point kernels (kan_fk.hip) */
+} kanode_eval_path;
 kanode_status kanode_set_option(kanode_handle* h, int32_t option, int64_t value);
 int64_t kanode_get_option(const kanode_handle* h, int32_t option);
 

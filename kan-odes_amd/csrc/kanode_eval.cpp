@@ -199,17 +199,21 @@ kanode_status rhs_t(kanode_handle* h, const T* p, const T* u, T* du, int64_t B, 
             if (h->opt.pp_on) {
                 HIP_TRY(h, kan::launch_fk_rhs_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co, (int)h->spec.nx, u, du,
                                                  B, st, table_build(h, h->built_phi), h->opt.grid_rhs));
+                served(h, KANODE_EVAL_FK_TABLE);
                 return KANODE_OK;
             }
         }
         HIP_TRY(h, kan::launch_fk_rhs<T>(h->hlc[0], h->dlc(), p, cd, co, (int)h->spec.nx, u, du, B, st));
+        served(h, KANODE_EVAL_FK_POINT);
         return KANODE_OK;
     }
     // (only here: a single column layer takes its own layer kernel, not the one-launch chain kernel)
     if (h->n_layers > 1 && all_col(h)) {
         bool done = false;
         const hipError_t e = kan::launch_kd_chain_col<T>(h->hlc, h->n_layers, h->dlc(), p, h->P, u, du, B, st);
-        if (kanode_status s = launched_or_error(h, e, "launch_kd_chain_col", done); s != KANODE_OK || done) return s;
+        if (kanode_status s = launched_or_error(h, e, "launch_kd_chain_col", done, KANODE_EVAL_CHAIN_KERNEL);
+            s != KANODE_OK || done)
+            return s;
     }
     kanode_status s = ensure_ws(h, B, st);
     if (s != KANODE_OK) return s;
@@ -220,8 +224,10 @@ kanode_status rhs_t(kanode_handle* h, const T* p, const T* u, T* du, int64_t B, 
         HIP_TRY(h, kan::launch_kd_fwd_widein<T>(h->hlc[0], h->dlc(), p, u, (T*)nullptr, ps, B, st));
         HIP_TRY(h, kan::launch_kd_fwd_wideout<T>(h->hlc[1], h->dlc() + 1, p, (const T*)nullptr, du, B, st, ps,
                                                   kan::widein_chunks(h->hlc[0])));
+        served(h, KANODE_EVAL_PAIR);
         return KANODE_OK;
     }
+    served(h, KANODE_EVAL_PER_LAYER);
     const T* cur = u;
     for (int l = 0; l < h->n_layers; ++l) {
         T* out = (l == h->n_layers - 1) ? du : ws + ((l % 2) ? wl.g1 : wl.g0);
@@ -249,11 +255,13 @@ kanode_status vjp_t(kanode_handle* h, const T* p, const T* u, const T* lam, T* l
                 HIP_TRY(h, kan::launch_fk_vjp_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co,
                                                  (int)h->spec.nx, u, lam, out, dp, (double*)h->slab.ptr(), kSlabBlocks, B,
                                                  st, table_build(h, h->built_vjp), h->opt.grid_vjp));
+                served(h, KANODE_EVAL_FK_TABLE);
                 return KANODE_OK;
             }
         }
         HIP_TRY(h, kan::launch_fk_vjp<T>(h->hlc[0], h->dlc(), p, cd, co, (int)h->spec.nx, u, lam, out, dp, (T*)h->slab.ptr(),
                                          kSlabBlocks, B, st));
+        served(h, KANODE_EVAL_FK_POINT);
         return KANODE_OK;
     }
     if (lamJ && h->n_in == h->n_out && all_col(h)) {
@@ -262,13 +270,16 @@ kanode_status vjp_t(kanode_handle* h, const T* p, const T* u, const T* lam, T* l
         const hipError_t e = kan::launch_kd_chain_vjp_stage<T>(h->hlc, h->n_layers, h->dlc(), p, h->P, u, none, lam,
                                                                none, nullptr, lamJ, dp, false, nullptr, h->slab.ptr(),
                                                                h->slab.bytes(), B, st);
-        if (kanode_status s = launched_or_error(h, e, "launch_kd_chain_vjp_stage", done); s != KANODE_OK || done) return s;
+        if (kanode_status s = launched_or_error(h, e, "launch_kd_chain_vjp_stage", done, KANODE_EVAL_CHAIN_KERNEL);
+            s != KANODE_OK || done)
+            return s;
     }
     kanode_status s = ensure_ws(h, B, st);
     if (s != KANODE_OK) return s;
     T* ws = (T*)h->ws.ptr();
     const WsLayout wl = ws_layout(h, B);
     if (surrogate_pair(h)) {
+        served(h, KANODE_EVAL_PAIR);
         T* ps = ws + wl.pslab;
         T* hbar = ws + wl.g0;
         const int nb = kan::widein_chunks(h->hlc[0]);
@@ -291,6 +302,7 @@ kanode_status vjp_t(kanode_handle* h, const T* p, const T* u, const T* lam, T* l
         return KANODE_OK;
     }
     // forward recompute, keeping every hidden layer's input
+    served(h, KANODE_EVAL_PER_LAYER);
     const T* acts[KANODE_MAX_LAYERS];
     acts[0] = u;
     T* wp = ws + wl.acts;
@@ -352,6 +364,7 @@ kanode_status stage_t(kanode_handle* h, const T* p, const T* u, const kanode_sta
                                                (int)h->spec.nx, u, sa, (double*)sg->y_out, (double*)h->slab.ptr(),
                                                kSlabBlocks, err_out, du, B, st, table_build(h, h->built_phi),
                                                h->opt.grid_rhs));
+            served(h, KANODE_EVAL_FK_TABLE);
             return KANODE_OK;
         }
     }
@@ -360,7 +373,9 @@ kanode_status stage_t(kanode_handle* h, const T* p, const T* u, const kanode_sta
         bool done = false;
         const hipError_t e = kan::launch_kd_chain_col<T>(h->hlc, h->n_layers, h->dlc(), p, h->P, u, du, B, st, &sa,
                                                          (T*)sg->y_out, (double*)h->slab.ptr(), kSlabBlocks, err_out);
-        if (kanode_status s = launched_or_error(h, e, "launch_kd_chain_col", done); s != KANODE_OK || done) return s;
+        if (kanode_status s = launched_or_error(h, e, "launch_kd_chain_col", done, KANODE_EVAL_CHAIN_KERNEL);
+            s != KANODE_OK || done)
+            return s;
     }
     const int64_t n = h->n_in * B;
     if (h->spec.rhs_kind == KANODE_RHS_CHAIN && surrogate_pair(h) && !skip) {
@@ -380,6 +395,7 @@ kanode_status stage_t(kanode_handle* h, const T* p, const T* u, const kanode_sta
         HIP_TRY(h, kan::launch_kd_fwd_wideout<T>(h->hlc[1], h->dlc() + 1, p, (const T*)nullptr, du, B, st, ps,
                                                   kan::widein_chunks(h->hlc[0])));
         if (err_out) HIP_TRY(h, kan::launch_stage_error<T>(u, y, du, sa, (double*)h->slab.ptr(), kSlabBlocks, err_out, n, st));
+        served(h, KANODE_EVAL_PAIR);
         return KANODE_OK;
     }
     // unfused: y materialised (into y_out or the handle's stage workspace), RHS, error pass
@@ -414,6 +430,7 @@ kanode_status vjp_stage_t(kanode_handle* h, const T* p, const T* u, const kanode
     if constexpr (std::is_same<T, double>::value) {
         // Fisher-KPP table path: the whole adjoint stage in one streaming kernel + one reduction
         if (fk_table_path(h) && lamJ && kan::fk_vjp_pp_supported(h->hlc[0], (int)h->spec.nx)) {
+            served(h, KANODE_EVAL_FK_TABLE);
             const auto [cd, co] = fk_lap(h);
             if (defer && (dp || err_out)) {
                 if (h->njobs == kan::kMaxFinishJobs && (s = vjp_flush(h, st)) != KANODE_OK) return s;
@@ -446,9 +463,11 @@ kanode_status vjp_stage_t(kanode_handle* h, const T* p, const T* u, const kanode
         const hipError_t e = kan::launch_kd_chain_vjp_stage<T>(h->hlc, h->n_layers, h->dlc(), p, h->P, u, su, lam, sl,
                                                                (T*)adj->y_out, lamJ, dp, dp_assign, err_out,
                                                                h->slab.ptr(), h->slab.bytes(), B, st);
-        if ((s = launched_or_error(h, e, "launch_kd_chain_vjp_stage", done)) != KANODE_OK || done) return s;
+        if ((s = launched_or_error(h, e, "launch_kd_chain_vjp_stage", done, KANODE_EVAL_CHAIN_KERNEL)) != KANODE_OK || done)
+            return s;
     }
     if (h->spec.rhs_kind == KANODE_RHS_CHAIN && surrogate_pair(h) && lamJ) {
+        served(h, KANODE_EVAL_PAIR);
         // surrogate pair: y and λs formed by the wide-in forward (no combination launches), the
         // parameter cotangents written with = when dp_assign (no memset): four launches per stage.
         // Deferred stages (the integrator's, `defer`) run lazily: a stage's second launch waits for the next
@@ -638,6 +657,7 @@ kanode_status kanode_layer_forward(kanode_handle* h, int32_t layer, const void* 
     const int64_t off = h->hlc[layer].p_off;
     hipStream_t st = (hipStream_t)stream;
     if ((s = ensure_ws(h, K, st)) != KANODE_OK) return s;
+    served(h, KANODE_EVAL_PER_LAYER);
     return by_dtype(h, [&](auto t) {
         using T = decltype(t);
         return layer_fwd_t<T>(h, layer, (const T*)p_layer - off, (const T*)x, (T*)y, K, st);
@@ -657,6 +677,7 @@ kanode_status kanode_layer_forward_stage(kanode_handle* h, int32_t layer, const 
     const int64_t off = h->hlc[layer].p_off;
     hipStream_t st = (hipStream_t)stream;
     if ((s = ensure_ws(h, K, st)) != KANODE_OK) return s;
+    served(h, KANODE_EVAL_PER_LAYER);
     return by_dtype(h, [&](auto t) {
         using T = decltype(t);
         return layer_fwd_stage_t<T>(h, layer, (const T*)p_layer - off, (const T*)x, sx, (const T*)lam, sl, (T*)out, K, st);
@@ -674,6 +695,7 @@ kanode_status kanode_layer_vjp(kanode_handle* h, int32_t layer, const void* p_la
     const int64_t off = h->hlc[layer].p_off;
     hipStream_t st = (hipStream_t)stream;
     if ((s = ensure_ws(h, K, st)) != KANODE_OK) return s;
+    served(h, KANODE_EVAL_PER_LAYER);
     return by_dtype(h, [&](auto t) {
         using T = decltype(t);
         return layer_vjp_t<T>(h, layer, (const T*)p_layer - off, (const T*)x, (const T*)ybar, (T*)xbar,

@@ -80,7 +80,7 @@ kanode_status kanode_internal_chain_step(kanode_handle* h, const void* p, const 
         return kan::launch_kd_chain_step<T>(h->hlc, h->n_layers, h->dlc(), (const T*)p, h->P, batch, a,
                                             (double*)h->slab.ptr(), kSlabBlocks, err_out, (hipStream_t)stream);
     });
-    return launched_or_error(h, e, "launch_kd_chain_step", launched);
+    return launched_or_error(h, e, "launch_kd_chain_step", launched, KANODE_EVAL_CHAIN_STEP);
 }
 
 // ---- one InterpolatingAdjoint step per launch ----
@@ -104,7 +104,7 @@ static kanode_status chain_adjoint_step_t(kanode_handle* h, const T* p, const ka
     for (int s = 0; s < (a.fsal ? 7 : 6); ++s) km[s] = (T*)km_out[s];
     const hipError_t e = kan::launch_kd_chain_vjp_step<T>(h->hlc, h->n_layers, h->dlc(), p, h->P, batch, a, (int)cap,
                                                           h->cstep_slab.ptr(), h->cstep_slab.bytes(), km, err_out, st);
-    return launched_or_error(h, e, "launch_kd_chain_vjp_step", launched);
+    return launched_or_error(h, e, "launch_kd_chain_vjp_step", launched, KANODE_EVAL_CHAIN_ADJ_STEP);
 }
 bool kanode_internal_chain_adjoint_step_ok(const kanode_handle* h) {
     if (h->spec.rhs_kind != KANODE_RHS_CHAIN || !h->opt.fused_step || !all_col(h)) return false;

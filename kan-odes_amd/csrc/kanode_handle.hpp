@@ -131,11 +131,17 @@ inline auto by_dtype(const kanode_handle* h, F&& f) {
     return by_dtype((int)h->spec.dtype, std::forward<F>(f));
 }
 
-// A launcher's answer: hipSuccess sets launched; hipErrorNotSupported means "not covered, the caller falls back"
-// (OK, launched untouched); anything else is an error named after the launcher.  No message is built otherwise.
-inline kanode_status launched_or_error(kanode_handle* h, hipError_t e, const char* what, bool& launched) {
+// KANODE_OPT_LAST_EVAL: the launcher that served this evaluation call (a kanode_eval_path value)
+inline void served(kanode_handle* h, kanode_eval_path path) { h->opt.last_eval = path; }
+
+// A launcher's answer: hipSuccess sets launched (and records `path` where the caller names one);
+// hipErrorNotSupported means "not covered, the caller falls back" (OK, launched untouched); anything else is an
+// error named after the launcher.  No message is built otherwise.
+inline kanode_status launched_or_error(kanode_handle* h, hipError_t e, const char* what, bool& launched,
+                                       kanode_eval_path path = KANODE_EVAL_NONE) {
     if (e == hipSuccess) {
         launched = true;
+        if (path != KANODE_EVAL_NONE) served(h, path);
         return KANODE_OK;
     }
     if (e == hipErrorNotSupported) return KANODE_OK;

@@ -27,13 +27,14 @@ struct HandleOptions {
     int pair_persist_max_wg = 0, pair_persist_abort = 0;
     int last_adjoint = KANODE_ADJ_NONE;
     int chain_wide = 1, record_adj_steps = 0, fk_loop = 1, fsens_wide = 0, train_any_chain = 0;
+    int last_eval = KANODE_EVAL_NONE;
 };
 
 enum OptionKind {
     OPT_FLAG,       // 0 or 1
     OPT_COUNT,      // 0..hi
     OPT_ONE_OF,     // PAIR_PERSIST_S: the kernel is instantiated for 4, 8 and 16 points per workgroup (0: its default)
-    OPT_READ_ONLY   // set by the library (kanode_internal_set_last_adjoint)
+    OPT_READ_ONLY   // set by the library (kanode_internal_set_last_adjoint, served)
 };
 struct OptionRow {
     int32_t id;
@@ -67,6 +68,7 @@ inline constexpr OptionRow kOptionTable[] = {
     {KANODE_OPT_FK_DEVICE_LOOP, "FK_DEVICE_LOOP", OPT_FLAG, 1, &HandleOptions::fk_loop},
     {KANODE_OPT_FSENS_WIDE, "FSENS_WIDE", OPT_COUNT, 2, &HandleOptions::fsens_wide},
     {KANODE_OPT_TRAIN_ANY_CHAIN, "TRAIN_ANY_CHAIN", OPT_FLAG, 1, &HandleOptions::train_any_chain},
+    {KANODE_OPT_LAST_EVAL, "LAST_EVAL", OPT_READ_ONLY, 0, &HandleOptions::last_eval},
 };
 
 inline const OptionRow* option_row(int32_t id) {

@@ -101,7 +101,11 @@ OPT_RECORD_ADJOINT_STEPS = 18
 OPT_FK_DEVICE_LOOP = 19
 OPT_FSENS_WIDE = 20        # 0 / 1 / 2 (include/kanode.h)
 OPT_TRAIN_ANY_CHAIN = 21   # 0 / 1: kanode_train_tsit5 on every small chain (Trainer(device_loop="any"))
+OPT_LAST_EVAL = 22         # read-only: a kanode_eval_path value
 ADJ_NONE, ADJ_HOST_LOOP, ADJ_CHAIN_WG, ADJ_PAIR_PERSIST, ADJ_PAIR_FALLBACK = 0, 1, 2, 3, 4   # kanode_adjoint_path
+# kanode_eval_path
+(EVAL_NONE, EVAL_CHAIN_KERNEL, EVAL_CHAIN_STEP, EVAL_CHAIN_ADJ_STEP, EVAL_PER_LAYER, EVAL_PAIR, EVAL_FK_TABLE,
+ EVAL_FK_POINT) = range(8)
 TRAIN_STOP = {0: "ok", 1: "forward_maxiters", 2: "dense_capacity", 3: "adjoint_maxiters", 4: "loss_not_finite",
               5: "test_maxiters"}   # kanode_train_stop
 OPTIONS = {"pointwise_table": OPT_POINTWISE_TABLE, "fused_step": OPT_FUSED_STEP, "fused_solve": OPT_FUSED_SOLVE,
@@ -112,7 +116,7 @@ OPTIONS = {"pointwise_table": OPT_POINTWISE_TABLE, "fused_step": OPT_FUSED_STEP,
            "pair_persist_abort": OPT_PAIR_PERSIST_ABORT, "last_adjoint": OPT_LAST_ADJOINT,
            "chain_wide": OPT_CHAIN_WIDE, "record_adjoint_steps": OPT_RECORD_ADJOINT_STEPS,
            "fk_device_loop": OPT_FK_DEVICE_LOOP, "fsens_wide": OPT_FSENS_WIDE,
-           "train_any_chain": OPT_TRAIN_ANY_CHAIN}
+           "train_any_chain": OPT_TRAIN_ANY_CHAIN, "last_eval": OPT_LAST_EVAL}
 
 SOLVE_STOP = {0: "ok", 1: "maxiters"}   # kanode_solve_stop
 

@@ -166,7 +166,7 @@ class KanodeHandle:
         """kanode_set_option by name (include/kanode.h; the names are _lib.OPTIONS: pointwise_table,
         fused_step, fused_solve, fused_solve_cap, grid_rhs, grid_vjp, grid_adj_step, adj_step_rows, pair_vjp,
         pair_fuse, pair_persist, pair_persist_s, adj_fused_finish, pair_persist_max_wg, pair_persist_abort,
-        fsens_wide, train_any_chain; last_adjoint is read-only)."""
+        fsens_wide, train_any_chain; last_adjoint and last_eval are read-only)."""
         if name not in L.OPTIONS:
             raise KeyError(f"unknown option {name!r}; known: {sorted(L.OPTIONS)}")
         L.check(L.lib().kanode_set_option(self._h, L.OPTIONS[name], int(value)), self._h, "kanode_set_option")

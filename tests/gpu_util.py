@@ -30,7 +30,7 @@ def specs_from_meta(meta):
 def cfgs_from_specs(specs):
     from kanode import LayerCfg
     return [LayerCfg(s.in_dims, s.out_dims, s.grid_len, s.normalizer, s.basis, s.use_base_act,
-                     tuple(s.grid_lims), None, s.iqf_reference_quirk) for s in specs]
+                     tuple(s.grid_lims), s.denominator, s.iqf_reference_quirk) for s in specs]
 
 
 def chain_scale(specs, p, u):

@@ -53,6 +53,7 @@ const Case kCases[] = {
     {19, 1, 0, 1, -1, 2, "FK_DEVICE_LOOP takes 0 or 1"},
     {20, 0, 0, 2, -1, 3, "FSENS_WIDE takes 0..2"},
     {21, 0, 0, 1, -1, 2, "TRAIN_ANY_CHAIN takes 0 or 1"},
+    // 22 = LAST_EVAL: read-only, below
 };
 
 void refused(HandleOptions& o, int32_t id, int64_t value, kanode_status want, const char* text, int64_t kept) {
@@ -94,6 +95,19 @@ void test_special_rows() {
     refused(o, 16, 1, KANODE_ERR_INVALID_ARG, "LAST_ADJOINT is read-only", 0);
     o.last_adjoint = 3;   // (as kanode_internal_set_last_adjoint does)
     CHECK(options_get(o, 16) == 3);
+    // LAST_EVAL: KANODE_EVAL_NONE = 0 until a call is served; never settable; its own field
+    CHECK(options_get(o, 22) == 0);
+    refused(o, 22, 0, KANODE_ERR_INVALID_ARG, "LAST_EVAL is read-only", 0);
+    refused(o, 22, 4, KANODE_ERR_INVALID_ARG, "LAST_EVAL is read-only", 0);
+    o.last_eval = KANODE_EVAL_FK_POINT;   // (as served() does)
+    CHECK(options_get(o, 22) == 7);
+    CHECK(options_get(o, 16) == 3);
+    o.last_adjoint = 0;
+    CHECK(options_get(o, 22) == 7);
+    // the eight paths, as include/kanode.h numbers them
+    CHECK(KANODE_EVAL_NONE == 0 && KANODE_EVAL_CHAIN_KERNEL == 1 && KANODE_EVAL_CHAIN_STEP == 2 &&
+          KANODE_EVAL_CHAIN_ADJ_STEP == 3 && KANODE_EVAL_PER_LAYER == 4 && KANODE_EVAL_PAIR == 5 &&
+          KANODE_EVAL_FK_TABLE == 6 && KANODE_EVAL_FK_POINT == 7);
     // PAIR_PERSIST_S: the instantiated workgroup sizes and 0
     const int64_t good[] = {0, 4, 8, 16}, bad[] = {1, 2, 5, 32};
     for (int64_t v : good) accepted(o, 12, v);
@@ -112,8 +126,8 @@ void test_special_rows() {
     CHECK(options_set(o, 1, 0, false, msg) == KANODE_OK && msg.empty());
     CHECK(options_get(o, 1) == 0);
     // unknown ids on either side of the enum
-    const int32_t unknown[] = {0, 22};
-    const char* text[] = {"unknown option 0", "unknown option 22"};
+    const int32_t unknown[] = {0, 23};
+    const char* text[] = {"unknown option 0", "unknown option 23"};
     for (int q = 0; q < 2; ++q) {
         msg.clear();
         CHECK(options_set(o, unknown[q], 0, true, msg) == KANODE_ERR_INVALID_ARG);
@@ -122,18 +136,18 @@ void test_special_rows() {
     }
 }
 
-// exactly one row per enum value 1..21: no gap, no duplicate, no two options sharing a field
+// exactly one row per enum value 1..22: no gap, no duplicate, no two options sharing a field
 void test_table_shape() {
-    int seen[22] = {};
+    int seen[23] = {};
     int rows = 0;
     for (const OptionRow& r : kOptionTable) {
-        CHECK(r.id >= 1 && r.id <= 21);
+        CHECK(r.id >= 1 && r.id <= 22);
         ++seen[r.id];
         ++rows;
         for (const OptionRow& q : kOptionTable) CHECK(&q == &r || q.field != r.field);
     }
-    CHECK(rows == 21);
-    for (int id = 1; id <= 21; ++id) CHECK(seen[id] == 1);
+    CHECK(rows == 22);
+    for (int id = 1; id <= 22; ++id) CHECK(seen[id] == 1);
 }
 
 // fits = "n <= k": the answer is min(k, hi), and 0 when nothing fits

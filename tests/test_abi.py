@@ -49,6 +49,9 @@ def test_option_ids_match_the_header():
     body = re.search(r"typedef enum \{([^}]*)\} kanode_adjoint_path;", src, flags=re.S).group(1)
     paths = {m.group(1): int(m.group(2)) for m in re.finditer(r"KANODE_ADJ_(\w+)\s*=\s*(\d+)", body)}
     assert paths == {n: getattr(L, "ADJ_" + n) for n in paths} and len(paths) == 5
+    body = re.search(r"typedef enum \{([^}]*)\} kanode_eval_path;", src, flags=re.S).group(1)
+    paths = {m.group(1): int(m.group(2)) for m in re.finditer(r"KANODE_EVAL_(\w+)\s*=\s*(\d+)", body)}
+    assert paths == {n: getattr(L, "EVAL_" + n) for n in paths} and len(paths) == 8
 
 
 def test_library_has_no_environment_knobs():

@@ -51,7 +51,8 @@ def test_header_binding_and_exports():
     assert set(ENTRIES) <= exported
     assert sorted(n for n in exported if "train" in n) == TRAIN_ENTRIES     # no exported name gained `train`
     assert not [n for n in ENTRIES if "train" in n or "_wg" in n or "any_chain" in n]
-    assert max(L.OPTIONS.values()) == 21                                    # and no handle option was added
+    # and the ensemble solve has no handle option of its own (21 = TRAIN_ANY_CHAIN, 22 = the read-only LAST_EVAL)
+    assert max(L.OPTIONS.values()) == 22 and not [n for n in L.OPTIONS if "ensemble" in n]
     assert kanode.lib().kanode_solve_ensemble_supported(None, 1) == 0
     assert kanode.lib().kanode_solve_ensemble_tsit5(None, 1, None, None, 1, 0.0, 1.0, None, 0, None, None, None, None,
                                                     None) == L.ERR_INVALID_ARG

@@ -15,7 +15,7 @@ from kanode import _lib as L
 pytestmark = pytest.mark.gpu
 
 # include/kanode.h: (default, a legal value that is not the default, an illegal value); pointwise_table's default
-# depends on the handle (1 where admissible) and is stated per handle below; last_adjoint is read-only
+# depends on the handle (1 where admissible) and is stated per handle below; last_adjoint and last_eval are read-only
 DOC = {
     "fused_step": (1, 0, 2), "fused_solve": (1, 0, -1), "fused_solve_cap": (0, 1 << 20, (1 << 20) + 1),
     "grid_rhs": (0, 1 << 24, (1 << 24) + 1), "grid_vjp": (0, 2048, 2049), "grid_adj_step": (0, 2048, 2049),
@@ -44,9 +44,10 @@ def _last_error(hd):
 @pytest.mark.parametrize("which", ["chain64", "fk64", "fk32"])
 def test_defaults_round_trip_and_refusal(handles, which):
     hd = handles[which]
-    assert set(L.OPTIONS) == set(DOC) | {"pointwise_table", "last_adjoint"}
+    assert set(L.OPTIONS) == set(DOC) | {"pointwise_table", "last_adjoint", "last_eval"}
     assert hd.get_option("pointwise_table") == TABLE_DEFAULT[which]
     assert hd.get_option("last_adjoint") == 0   # KANODE_ADJ_NONE: no adjoint on this handle yet
+    assert hd.get_option("last_eval") == L.EVAL_NONE == 0   # no evaluation on this handle yet
     for name, (dflt, legal, illegal) in DOC.items():
         assert hd.get_option(name) == dflt, name
         hd.set_option(name, legal)
@@ -59,8 +60,11 @@ def test_defaults_round_trip_and_refusal(handles, which):
     with pytest.raises(kanode.KanodeError, match="LAST_ADJOINT is read-only"):
         hd.set_option("last_adjoint", 1)
     assert hd.get_option("last_adjoint") == 0
+    with pytest.raises(kanode.KanodeError, match="LAST_EVAL is read-only"):
+        hd.set_option("last_eval", 1)
+    assert hd.get_option("last_eval") == 0
     # ids on either side of the enum
-    for bad in (0, 22):
+    for bad in (0, 23):
         assert L.lib().kanode_get_option(hd._h, bad) == -1
         assert L.lib().kanode_set_option(hd._h, bad, 0) == L.ERR_INVALID_ARG
         assert _last_error(hd) == f"unknown option {bad}"

@@ -25,7 +25,8 @@ def test_option_id_and_documented_default():
     body = re.search(r"typedef enum \{([^}]*)\} kanode_option;", src, flags=re.S).group(1)
     assert re.search(r"KANODE_OPT_TRAIN_ANY_CHAIN\s*=\s*21\b", body)
     assert L.OPTIONS["train_any_chain"] == 21 == L.OPT_TRAIN_ANY_CHAIN
-    assert max(L.OPTIONS.values()) == 21 and len(set(L.OPTIONS.values())) == len(L.OPTIONS)
+    # (one option follows it: the read-only LAST_EVAL = 22)
+    assert max(L.OPTIONS.values()) == 22 == L.OPT_LAST_EVAL and len(set(L.OPTIONS.values())) == len(L.OPTIONS)
     assert re.search(r"KANODE_OPT_TRAIN_ANY_CHAIN \(default 0\)", src)
 
 
