@@ -425,6 +425,20 @@ int64_t kanode_adjoint_step_sizes(const kanode_handle* h, double* out, int64_t c
    its last build rejected (their points take the direct formula), -1 for a table not built yet.  Synchronous
    (reads the device stamps after the handle's work); KANODE_ERR_UNSUPPORTED without a table path. */
 kanode_status kanode_table_rejections(kanode_handle* h, int32_t out[3]);
+/* Which Fisher-KPP table kernel the handle launched last, and how (no reference counterpart; host state only, no
+   synchronisation).  KANODE_OPT_LAST_EVAL says KANODE_EVAL_FK_TABLE for all of them; this names the launch:
+     out[0] family: 0 none yet, 1 pair short, 2 pair long, 3 wave RHS, 4 stage, 5 step, 6 step loop, 7 VJP,
+            8 VJP stage, 9 adjoint step (rows), 10 adjoint step (wave), 11 adjoint loop
+     out[1] NP, the 128-point segments of a row (1, 2, 4; 0 for the pair kernels)
+     out[2] normalizer class of the kernel: 2 softsign, 0 tanh_fast, -1 runtime
+     out[3] PATH of a VJP family (7..11): 1 recurrence, 2 corrected recurrence; -1 otherwise
+     out[4] GT of a VJP family (5 or 10); 0 otherwise
+     out[5] bit 0: the kernel has the interval count 256 at compile time; bits 1-2: the adjoint step's
+            combine as launched (0, 1 fixed, 2 adaptive); bit 3: the finish ran fused in the step launch
+     out[6] chunk: rows per wave of a batch-covering grid; 0 for a persistent (grid-stride) launch
+     out[7] grid: workgroups launched
+   The integrator's step, loop and adjoint launches are recorded like the evaluation calls'. */
+kanode_status kanode_last_fk_launch(kanode_handle* h, int32_t out[8]);
 
 /* --- the optimiser step after the gradient all-reduce -----------
  * Flux 0.14 Optimise.Adam + update!(opt, x, Δ) (LV_driver_KANODE.jl:219,287; Fisher-KPP_Source.jl:

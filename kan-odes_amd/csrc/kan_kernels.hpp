@@ -135,9 +135,23 @@ struct GridOverride {
 };
 hipError_t launch_fk_pp_build(const PPConst& hpc, const LayerConst* lc, const PPConst* pc, const double* p,
                               double* tables, const int* fns, int nfn, hipStream_t st);
+// What a table launcher launched (kanode_last_fk_launch): every launcher below takes an optional FkLaunchRec* as
+// its last argument and stores the launch there once, on the host.  norm: the kernel's NORM (NORM_SOFTSIGN,
+// NORM_TANH_FAST or NORM_RUNTIME); np: the 128-point segments per row (0: the pair kernels); path / gt: the VJP
+// families' PATH and GT, else -1 / 0; ni_ct: the compile-time NI (256)
+// or 0 for the runtime-ni kernels; chunk: rows per wave of a batch-covering grid, 0 for the persistent form;
+// combine / fused_finish: as launched by the adjoint step (0 elsewhere).
+enum FkFamily {
+    FK_FAM_NONE = 0, FK_FAM_PAIR_SHORT, FK_FAM_PAIR_LONG, FK_FAM_WAVE_RHS, FK_FAM_STAGE, FK_FAM_STEP,
+    FK_FAM_STEP_LOOP, FK_FAM_VJP, FK_FAM_VJP_STAGE, FK_FAM_ADJ_STEP_ROWS, FK_FAM_ADJ_STEP_WAVE, FK_FAM_ADJ_LOOP
+};
+struct FkLaunchRec {
+    int32_t family = FK_FAM_NONE, np = 0, norm = 0, path = -1, gt = 0, ni_ct = 0, chunk = 0, grid = 0, combine = 0,
+            fused_finish = 0;
+};
 hipError_t launch_fk_rhs_pp(const PPConst& hpc, const LayerConst& hlc, const LayerConst* lc, const PPConst* pc, const double* p,
                             double* table, double cd, double co, int Nx, const double* u, double* du, int64_t B,
-                            hipStream_t st, bool build = true, int grid_ovr = 0);
+                            hipStream_t st, bool build = true, int grid_ovr = 0, FkLaunchRec* rec = nullptr);
 bool fk_vjp_pp_supported(const LayerConst& hlc, int Nx);
 bool fk_stage_pp_supported(const PPConst& hpc, int Nx);
 // fused stage: du = f(u + Σ c_j k_j), optional y_out, optional error total into err_out[0]
@@ -145,7 +159,7 @@ hipError_t launch_fk_stage_pp(const PPConst& hpc, const LayerConst& hlc, const L
                               const double* p, double* table, double cd, double co, int Nx, const double* u,
                               const StageArgs<double>& sa, double* y_out, double* err_slab, int slab_blocks,
                               double* err_out, double* du, int64_t B, hipStream_t st, bool build = true,
-                              int grid_ovr = 0);
+                              int grid_ovr = 0, FkLaunchRec* rec = nullptr);
 // A whole Tsit5 step of the Fisher-KPP table RHS per trajectory row (fk_step_pp_wave_kernel):
 // a6x6[6s + j] = dt·a_sj, e7 = dt·btilde (error with err_out), k_2..k_7 -> kout[0..5]; with
 // q4x7[7m + i] = dt·RI[i][m] the dense output is Q_1..Q_4 -> kout[0..3] and k_7 -> kout[5]
@@ -154,7 +168,7 @@ hipError_t launch_fk_step_pp(const PPConst& hpc, const LayerConst& hlc, const La
                              const double* k1, double* const* kout, double* u_new, const double* a6x6,
                              const double* e7, const double* q4x7, double abstol, double reltol, double* err_slab,
                              int slab_blocks, double* err_out, int64_t B, hipStream_t st, bool build,
-                             int grid_ovr = 0, int* parts_out = nullptr);
+                             int grid_ovr = 0, int* parts_out = nullptr, FkLaunchRec* rec = nullptr);
 // (parts_out != nullptr with err_out: the per-block error partials are left in err_slab[0, *parts_out)
 // for the caller to sum -- the host, from mapped memory -- instead of a final reduction launch)
 
@@ -197,14 +211,15 @@ bool fk_adjoint_loop_supported(const PPConst& hpc, const LayerConst& hlc, int Nx
 int fk_adjoint_loop_grid(int64_t B, int slab_blocks);
 hipError_t launch_fk_adjoint_loop(const PPConst& hpc, const LayerConst& hlc, const LayerConst* lc, const PPConst* pc,
                                   const double* p, double* tables, double cd, double co, int Nx, const AdjLoopArgs& la,
-                                  int64_t B, hipStream_t st, bool build);
+                                  int64_t B, hipStream_t st, bool build, FkLaunchRec* rec = nullptr);
 hipError_t launch_fk_step_pp_loop(const PPConst& hpc, const LayerConst& hlc, const LayerConst* lc, double cd,
                                   double co, int Nx, const double* p, const double* table, const FkLoopArgs& la,
-                                  int64_t lq, int64_t B, hipStream_t st, int grid_ovr = 0);
+                                  int64_t lq, int64_t B, hipStream_t st, int grid_ovr = 0,
+                                  FkLaunchRec* rec = nullptr);
 hipError_t launch_fk_vjp_pp(const PPConst& hpc, const LayerConst& hlc, const LayerConst* lc, const PPConst* pc,
                             const double* p, double* tables, double cd, double co, int Nx, const double* u,
                             const double* lam, double* lamJ, double* dp, double* slab, int slab_blocks, int64_t B,
-                            hipStream_t st, bool build = true, int grid_ovr = 0);
+                            hipStream_t st, bool build = true, int grid_ovr = 0, FkLaunchRec* rec = nullptr);
 // adjoint stage, fused (kanode_vjp_stage): y = u + Σ su.c_j su.k_j, λs = lam + Σ sl.c_j sl.k_j
 // in registers (λs -> lam_out if non-null), λᵀJ at y, dp (= if dp_assign, else +=), the λ
 // error total -> err_out[0] when non-null (sl.ec / abstol / reltol)
@@ -213,7 +228,7 @@ hipError_t launch_fk_vjp_stage_pp(const PPConst& hpc, const LayerConst& hlc, con
                                   const StageArgs<double>& su, const double* lam, const StageArgs<double>& sl,
                                   double* lam_out, double* lamJ, double* dp, bool dp_assign, double* err_out,
                                   double* slab, int slab_blocks, int64_t B, hipStream_t st, bool build = true,
-                                  int* deferred_grid = nullptr, int grid_ovr = 0);
+                                  int* deferred_grid = nullptr, int grid_ovr = 0, FkLaunchRec* rec = nullptr);
 // The reductions of several adjoint stages launched with deferred_grid (their slabs in
 // separate regions) in one launch: job j sums slab_j rows into dp_j (= or +=) and err_slab_j
 // into err_out_j, each in the fixed order of vjp_finish_kernel.
@@ -272,7 +287,8 @@ hipError_t launch_fk_vjp_step_pp(const PPConst& hpc, const LayerConst& hlc, cons
                                  const double* p, double* tables, double cd, double co, int Nx,
                                  const AdjStepArgs& a, double* slab_base, int slab_blocks, int64_t B, int* grid_out,
                                  hipStream_t st, bool build, int grid_ovr = 0, bool rows = true,
-                                 int* combined_out = nullptr, bool* fused_finish_out = nullptr);
+                                 int* combined_out = nullptr, bool* fused_finish_out = nullptr,
+                                 FkLaunchRec* rec = nullptr);
 constexpr int kMaxFinishJobs = 8;
 struct FinishJob {
     const double* slab;

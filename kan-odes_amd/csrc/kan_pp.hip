@@ -1631,9 +1631,19 @@ hipError_t launch_fk_pp_build(const PPConst& hpc, const LayerConst* lc, const PP
 #endif
 constexpr int kPPChunk = KAN_PP_CHUNK;   // rows per wave of the table RHS kernel (0 = persistent grid)
 
+// the launch record (kan_kernels.hpp FkLaunchRec): one host-side store per launch, where the caller asks
+static inline void fk_rec(FkLaunchRec* rec, int family, int np, int norm, int path, int gt, int ni_ct, int chunk,
+                          int grid, int combine = 0, bool fused = false) {
+    if (!rec) return;
+    FkLaunchRec r;
+    r.family = family, r.np = np, r.norm = norm, r.path = path, r.gt = gt, r.ni_ct = ni_ct, r.chunk = chunk;
+    r.grid = grid, r.combine = combine, r.fused_finish = fused ? 1 : 0;
+    *rec = r;
+}
+
 hipError_t launch_fk_rhs_pp(const PPConst& hpc, const LayerConst& hlc, const LayerConst* lc, const PPConst* pc, const double* p,
                             double* table, double cd, double co, int Nx, const double* u, double* du, int64_t B,
-                            hipStream_t st, bool build, int grid_ovr) {
+                            hipStream_t st, bool build, int grid_ovr, FkLaunchRec* rec) {
     if (Nx < 2 || (Nx & 1)) return hipErrorInvalidValue;
     const int fn_phi = PP_PHI;
     if (build) {
@@ -1653,6 +1663,7 @@ hipError_t launch_fk_rhs_pp(const PPConst& hpc, const LayerConst& hlc, const Lay
                                    : grid_for(B, kRhsBlock / kWave, grid_ovr > 0 ? grid_ovr : cap);             \
         hipLaunchKernelGGL((fk_rhs_pp_wave_kernel<NORM, BASIS, NP>), dim3(grid), dim3(kRhsBlock), lds, st, lc, p, \
                            (const double2*)table, hpc.ni, hpc.inv_w, hpc.x0, cd, co, u, du, B, chunk);           \
+        fk_rec(rec, FK_FAM_WAVE_RHS, NP, NORM, -1, 0, 0, chunk, grid);                                           \
     } while (0)
 #define KAN_PP_PAIR(NORM, BASIS, SHORT)                                                                          \
     do {                                                                                                         \
@@ -1661,6 +1672,7 @@ hipError_t launch_fk_rhs_pp(const PPConst& hpc, const LayerConst& hlc, const Lay
         const int grid = grid_for(B, tpb, cap);                                                                  \
         hipLaunchKernelGGL((fk_rhs_pp_kernel<NORM, BASIS, SHORT>), dim3(grid), dim3(kBlock), lds, st, lc, p,     \
                            (const double2*)table, hpc.ni, hpc.inv_w, hpc.x0, cd, co, Nx, tl, u, du, B);          \
+        fk_rec(rec, SHORT ? FK_FAM_PAIR_SHORT : FK_FAM_PAIR_LONG, 0, NORM, -1, 0, 0, 0, grid);                   \
     } while (0)
 #define KAN_PP_GO(NORM, BASIS)                                                                                   \
     do {                                                                                                         \
@@ -1684,7 +1696,8 @@ bool fk_stage_pp_supported(const PPConst& hpc, int Nx) { return hpc.enabled && (
 hipError_t launch_fk_stage_pp(const PPConst& hpc, const LayerConst& hlc, const LayerConst* lc, const PPConst* pc,
                               const double* p, double* table, double cd, double co, int Nx, const double* u,
                               const StageArgs<double>& sa, double* y_out, double* err_slab, int slab_blocks,
-                              double* err_out, double* du, int64_t B, hipStream_t st, bool build, int grid_ovr) {
+                              double* err_out, double* du, int64_t B, hipStream_t st, bool build, int grid_ovr,
+                              FkLaunchRec* rec) {
     if (!fk_stage_pp_supported(hpc, Nx)) return hipErrorInvalidValue;
     const int fn_phi = PP_PHI;
     hipError_t e = hipSuccess;
@@ -1700,6 +1713,7 @@ hipError_t launch_fk_stage_pp(const PPConst& hpc, const LayerConst& hlc, const L
         grid = grid_for(B, kBlock / kWave, gcap < slab_blocks ? gcap : slab_blocks);                            \
         hipLaunchKernelGGL((fk_stage_pp_wave_kernel<NORM, BASIS, NP>), dim3(grid), dim3(kBlock), lds, st, lc, p, \
                            (const double2*)table, hpc.ni, hpc.inv_w, hpc.x0, cd, co, u, sa, y_out, slab, du, B);  \
+        fk_rec(rec, FK_FAM_STAGE, NP, NORM, -1, 0, 0, 0, grid);                                                  \
     } while (0)
 #define KAN_STAGE_GO(NORM, BASIS)                                                                                \
     do {                                                                                                         \
@@ -1722,7 +1736,7 @@ hipError_t launch_fk_step_pp(const PPConst& hpc, const LayerConst& hlc, const La
                              const double* k1, double* const* kout, double* u_new, const double* a6x6,
                              const double* e7, const double* q4x7, double abstol, double reltol, double* err_slab,
                              int slab_blocks, double* err_out, int64_t B, hipStream_t st, bool build, int grid_ovr,
-                             int* parts_out) {
+                             int* parts_out, FkLaunchRec* rec) {
     if (!fk_stage_pp_supported(hpc, Nx)) return hipErrorInvalidValue;
     const int fn_phi = PP_PHI;
     hipError_t e = hipSuccess;
@@ -1752,6 +1766,7 @@ hipError_t launch_fk_step_pp(const PPConst& hpc, const LayerConst& hlc, const La
         hipLaunchKernelGGL((fk_step_pp_wave_kernel<NORM, BASIS, NP>), dim3(grid), dim3(kBlock), lds, st, lc, p,  \
                            (const double2*)table, hpc.ni, hpc.inv_w, hpc.x0, cd, co, u, k1, so, sc, slab, B,    \
                            FkLoopArgs{}, (int64_t)0);                                                            \
+        fk_rec(rec, FK_FAM_STEP, NP, NORM, -1, 0, 0, 0, grid);                                                   \
     } while (0)
 #define KAN_STEP_GO(NORM, BASIS)                                                                                 \
     do {                                                                                                         \
@@ -1777,7 +1792,7 @@ hipError_t launch_fk_step_pp(const PPConst& hpc, const LayerConst& hlc, const La
 // most la.max_grid workgroups (the same grid every launch).  The tables must already be built.
 hipError_t launch_fk_step_pp_loop(const PPConst& hpc, const LayerConst& hlc, const LayerConst* lc, double cd,
                                   double co, int Nx, const double* p, const double* table, const FkLoopArgs& la,
-                                  int64_t lq, int64_t B, hipStream_t st, int grid_ovr) {
+                                  int64_t lq, int64_t B, hipStream_t st, int grid_ovr, FkLaunchRec* rec) {
     const int max_grid = (int)la.max_grid;
     if (!fk_stage_pp_supported(hpc, Nx)) return hipErrorInvalidValue;
     const size_t lds = sizeof(double2) * (kPPCoef / 2) * (size_t)hpc.ni;
@@ -1790,6 +1805,7 @@ hipError_t launch_fk_step_pp_loop(const PPConst& hpc, const LayerConst& hlc, con
         hipLaunchKernelGGL((fk_step_pp_wave_kernel<NORM, BASIS, NP, true>), dim3(grid), dim3(kBlock), lds, st,  \
                            lc, p, (const double2*)table, hpc.ni, hpc.inv_w, hpc.x0, cd, co, nullptr, nullptr,  \
                            StepOut{}, StepCoef{}, nullptr, B, la, lq);                                           \
+        fk_rec(rec, FK_FAM_STEP_LOOP, NP, NORM, -1, 0, 0, 0, grid);                                              \
     } while (0)
 #define KAN_LOOP_GO(NORM, BASIS)                                                                                 \
     do {                                                                                                         \
@@ -1819,7 +1835,7 @@ static hipError_t fk_vjp_pp_go(const PPConst& hpc, const LayerConst* lc, const d
                                double cd, double co, int Nx, const double* u, const double* lam, double* lamJ,
                                double* slab, int slab_blocks, int64_t B, int& grid, const StageArgs<double>& su,
                                const StageArgs<double>& sl, double* lam_out, double* err_slab, hipStream_t st,
-                               int grid_ovr) {
+                               int grid_ovr, FkLaunchRec* rec) {
     const size_t lds = 2 * sizeof(double2) * (kPPCoef / 2) * (size_t)hpc.ni;
 #define KAN_VJP_WAVE(NP, NI)                                                                                      \
     do {                                                                                                         \
@@ -1841,6 +1857,7 @@ static hipError_t fk_vjp_pp_go(const PPConst& hpc, const LayerConst* lc, const d
         hipLaunchKernelGGL((fk_vjp_pp_wave_kernel<NORM, PATH, GT, NP, STG, NI>), dim3(grid), dim3(kVjpBlock), lds, st, \
                            lc, p, (const double2*)tables, hpc.ni, hpc.inv_w, hpc.x0, cd, co, u, lam, lamJ, slab, B, \
                            su, sl, lam_out, err_slab ? slab + (int64_t)grid * (GT + 1) : nullptr, chunk);        \
+        fk_rec(rec, STG ? FK_FAM_VJP_STAGE : FK_FAM_VJP, NP, NORM, PATH, GT, NI, chunk, grid);                   \
     } while (0)
     if (Nx == 256 && !STG && hpc.ni == 256) KAN_VJP_WAVE(2, 256);   // the FK256 tables (w = 1/32 on [-4, 4))
     else if (Nx == 256) KAN_VJP_WAVE(2, 0);
@@ -1855,10 +1872,11 @@ static hipError_t fk_vjp_pp_dispatch(const PPConst& hpc, const LayerConst& hlc, 
                                      const double* tables, double cd, double co, int Nx, const double* u,
                                      const double* lam, double* lamJ, double* slab, int slab_blocks, int64_t B,
                                      int& grid, const StageArgs<double>& su, const StageArgs<double>& sl,
-                                     double* lam_out, double* err_slab, hipStream_t st, int grid_ovr) {
+                                     double* lam_out, double* err_slab, hipStream_t st, int grid_ovr,
+                                     FkLaunchRec* rec) {
 #define KAN_VJP_GO(NORM, PATH, GT)                                                                               \
     return fk_vjp_pp_go<NORM, PATH, GT, STG>(hpc, lc, p, tables, cd, co, Nx, u, lam, lamJ, slab, slab_blocks, B, \
-                                             grid, su, sl, lam_out, err_slab, st, grid_ovr)
+                                             grid, su, sl, lam_out, err_slab, st, grid_ovr, rec)
     if (hlc.path == PATH_REC_CORR) {
         if (hlc.G == 10 && hlc.norm == NORM_SOFTSIGN) KAN_VJP_GO(NORM_SOFTSIGN, PATH_REC_CORR, 10);
         else if (hlc.G == 10) KAN_VJP_GO(NORM_TANH_FAST, PATH_REC_CORR, 10);
@@ -1876,7 +1894,7 @@ static hipError_t fk_vjp_pp_dispatch(const PPConst& hpc, const LayerConst& hlc, 
 hipError_t launch_fk_vjp_pp(const PPConst& hpc, const LayerConst& hlc, const LayerConst* lc, const PPConst* pc,
                             const double* p, double* tables, double cd, double co, int Nx, const double* u,
                             const double* lam, double* lamJ, double* dp, double* slab, int slab_blocks, int64_t B,
-                            hipStream_t st, bool build, int grid_ovr) {
+                            hipStream_t st, bool build, int grid_ovr, FkLaunchRec* rec) {
     if (!fk_vjp_pp_supported(hlc, Nx)) return hipErrorInvalidValue;
     const int fns[2] = {PP_DPHI, PP_SWISH};
     hipError_t e = hipSuccess;
@@ -1884,7 +1902,7 @@ hipError_t launch_fk_vjp_pp(const PPConst& hpc, const LayerConst& hlc, const Lay
     int grid = 0;
     const StageArgs<double> none{};
     e = fk_vjp_pp_dispatch<false>(hpc, hlc, lc, p, tables, cd, co, Nx, u, lam, lamJ, slab, slab_blocks, B, grid, none,
-                                  none, nullptr, nullptr, st, grid_ovr);
+                                  none, nullptr, nullptr, st, grid_ovr, rec);
     if (e != hipSuccess || !dp) return e;
     return launch_slab_reduce<double>(slab, grid, hlc.G + (hlc.use_base ? 1 : 0), dp, st);
 }
@@ -1894,7 +1912,7 @@ hipError_t launch_fk_vjp_stage_pp(const PPConst& hpc, const LayerConst& hlc, con
                                   const StageArgs<double>& su, const double* lam, const StageArgs<double>& sl,
                                   double* lam_out, double* lamJ, double* dp, bool dp_assign, double* err_out,
                                   double* slab, int slab_blocks, int64_t B, hipStream_t st, bool build,
-                                  int* deferred_grid, int grid_ovr) {
+                                  int* deferred_grid, int grid_ovr, FkLaunchRec* rec) {
     if (!fk_vjp_pp_supported(hlc, Nx)) return hipErrorInvalidValue;
     const int fns[2] = {PP_DPHI, PP_SWISH};
     hipError_t e = hipSuccess;
@@ -1904,7 +1922,7 @@ hipError_t launch_fk_vjp_stage_pp(const PPConst& hpc, const LayerConst& hlc, con
     // with deferred_grid the reduction is left to launch_vjp_finish_jobs
     const int cap = slab_blocks / 2;
     e = fk_vjp_pp_dispatch<true>(hpc, hlc, lc, p, tables, cd, co, Nx, u, lam, lamJ, slab, cap, B, grid, su, sl,
-                                 lam_out, err_out ? slab : nullptr, st, grid_ovr);
+                                 lam_out, err_out ? slab : nullptr, st, grid_ovr, rec);
     if (e != hipSuccess) return e;
     const int P = hlc.G + (hlc.use_base ? 1 : 0);
     if (deferred_grid) {
@@ -1922,7 +1940,7 @@ hipError_t launch_fk_vjp_step_pp(const PPConst& hpc, const LayerConst& hlc, cons
                                  const double* p, double* tables, double cd, double co, int Nx,
                                  const AdjStepArgs& a_in, double* slab_base, int slab_blocks, int64_t B,
                                  int* grid_out, hipStream_t st, bool build, int grid_ovr, bool rows,
-                                 int* combined_out, bool* fused_finish_out) {
+                                 int* combined_out, bool* fused_finish_out, FkLaunchRec* rec) {
     if (!fk_vjp_pp_supported(hlc, Nx)) return hipErrorInvalidValue;
     const int fns[2] = {PP_DPHI, PP_SWISH};
     hipError_t e = hipSuccess;
@@ -1985,6 +2003,8 @@ hipError_t launch_fk_vjp_step_pp(const PPConst& hpc, const LayerConst& hlc, cons
                 hipLaunchKernelGGL((fk_vjp_step_rows_kernel<NORM, PATH, GT, (NP < 4 ? NP : 2), 0>), dim3(grid),    \
                                    dim3(kVjpBlock), lds, st, lc, p, (const double2*)tables, hpc.ni, hpc.inv_w,    \
                                    hpc.x0, cd, co, B, a);                                       \
+            fk_rec(rec, FK_FAM_ADJ_STEP_ROWS, NP, NORM, PATH, GT,                                                \
+                   KAN_VROWS_NI && NP == 2 && hpc.ni == 256 ? 256 : 0, 0, grid, a.combine, a.fin_ctr != nullptr); \
             break;                                                                                               \
         }                                                                                                        \
         static int cap = 0;                                                                                      \
@@ -1995,6 +2015,7 @@ hipError_t launch_fk_vjp_step_pp(const PPConst& hpc, const LayerConst& hlc, cons
         if (a.err_slab) a.err_slab = slab_base + (int64_t)6 * grid * P;                                           \
         hipLaunchKernelGGL((fk_vjp_step_pp_wave_kernel<NORM, PATH, GT, NP>), dim3(grid), dim3(kVjpBlock), lds, st,  \
                            lc, p, (const double2*)tables, hpc.ni, hpc.inv_w, hpc.x0, cd, co, B, a);              \
+        fk_rec(rec, FK_FAM_ADJ_STEP_WAVE, NP, NORM, PATH, GT, 0, 0, grid, a.combine, a.fin_ctr != nullptr);       \
     } while (0)
 #define KAN_VSTEP_NP(NORM, PATH, GT)                                                                              \
     do {                                                                                                         \
@@ -2030,7 +2051,7 @@ int fk_adjoint_loop_grid(int64_t B, int slab_blocks) {   // the rows step's grid
 }
 hipError_t launch_fk_adjoint_loop(const PPConst& hpc, const LayerConst& hlc, const LayerConst* lc, const PPConst* pc,
                                   const double* p, double* tables, double cd, double co, int Nx, const AdjLoopArgs& la,
-                                  int64_t B, hipStream_t st, bool build) {
+                                  int64_t B, hipStream_t st, bool build, FkLaunchRec* rec) {
     if (!fk_adjoint_loop_supported(hpc, hlc, Nx) || la.grid < 1) return hipErrorInvalidValue;
     const int fns[2] = {PP_DPHI, PP_SWISH};
     hipError_t e = hipSuccess;
@@ -2050,6 +2071,8 @@ hipError_t launch_fk_adjoint_loop(const PPConst& hpc, const LayerConst& hlc, con
             hipLaunchKernelGGL((fk_vjp_step_rows_loop_kernel<NORM, PATH, GT, 1, 2, 0>), dim3(la.grid),            \
                                dim3(kVjpBlock), lds, st, lc, p, (const double2*)tables, hpc.ni, hpc.inv_w, hpc.x0,  \
                                cd, co, B, la.ctl, la.plan);                                                 \
+        fk_rec(rec, FK_FAM_ADJ_LOOP, Nx == 256 ? 2 : 1, NORM, PATH, GT, Nx == 256 && hpc.ni == 256 ? 256 : 0, 0, \
+               (int)la.grid, 2, false); /* (the finish is the launch that follows) */                            \
     } while (0)
     if (hlc.path == PATH_REC_CORR) {
         if (hlc.G == 10 && hlc.norm == NORM_SOFTSIGN) KAN_ALOOP(NORM_SOFTSIGN, PATH_REC_CORR, 10);

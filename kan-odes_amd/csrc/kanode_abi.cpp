@@ -417,6 +417,20 @@ kanode_status kanode_table_rejections(kanode_handle* h, int32_t out[3]) {
     return KANODE_OK;
 }
 
+kanode_status kanode_last_fk_launch(kanode_handle* h, int32_t out[8]) {
+    if (!h || !out) return KANODE_ERR_INVALID_ARG;
+    const kan::FkLaunchRec& r = h->fk_launch;
+    out[0] = r.family;
+    out[1] = r.np;
+    out[2] = r.norm;
+    out[3] = r.path;
+    out[4] = r.gt;
+    out[5] = (r.ni_ct == 256 ? 1 : 0) | (r.combine << 1) | (r.fused_finish << 3);
+    out[6] = r.chunk;
+    out[7] = r.grid;
+    return KANODE_OK;
+}
+
 int64_t kanode_adjoint_step_sizes(const kanode_handle* h, double* out, int64_t cap) {
     if (!h) return -1;
     const int64_t n = (int64_t)h->adj_steps.size();

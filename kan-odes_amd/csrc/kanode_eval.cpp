@@ -198,7 +198,8 @@ kanode_status rhs_t(kanode_handle* h, const T* p, const T* u, T* du, int64_t B, 
         if constexpr (std::is_same<T, double>::value) {
             if (h->opt.pp_on) {
                 HIP_TRY(h, kan::launch_fk_rhs_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co, (int)h->spec.nx, u, du,
-                                                 B, st, table_build(h, h->built_phi), h->opt.grid_rhs));
+                                                 B, st, table_build(h, h->built_phi), h->opt.grid_rhs,
+                                                 &h->fk_launch));
                 served(h, KANODE_EVAL_FK_TABLE);
                 return KANODE_OK;
             }
@@ -254,7 +255,7 @@ kanode_status vjp_t(kanode_handle* h, const T* p, const T* u, const T* lam, T* l
             if (h->opt.pp_on && kan::fk_vjp_pp_supported(h->hlc[0], (int)h->spec.nx)) {
                 HIP_TRY(h, kan::launch_fk_vjp_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co,
                                                  (int)h->spec.nx, u, lam, out, dp, (double*)h->slab.ptr(), kSlabBlocks, B,
-                                                 st, table_build(h, h->built_vjp), h->opt.grid_vjp));
+                                                 st, table_build(h, h->built_vjp), h->opt.grid_vjp, &h->fk_launch));
                 served(h, KANODE_EVAL_FK_TABLE);
                 return KANODE_OK;
             }
@@ -363,7 +364,7 @@ kanode_status stage_t(kanode_handle* h, const T* p, const T* u, const kanode_sta
             HIP_TRY(h, kan::launch_fk_stage_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co,
                                                (int)h->spec.nx, u, sa, (double*)sg->y_out, (double*)h->slab.ptr(),
                                                kSlabBlocks, err_out, du, B, st, table_build(h, h->built_phi),
-                                               h->opt.grid_rhs));
+                                               h->opt.grid_rhs, &h->fk_launch));
             served(h, KANODE_EVAL_FK_TABLE);
             return KANODE_OK;
         }
@@ -440,7 +441,8 @@ kanode_status vjp_stage_t(kanode_handle* h, const T* p, const T* u, const kanode
                 HIP_TRY(h, kan::launch_fk_vjp_stage_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co,
                                                        (int)h->spec.nx, u, su, lam, sl, (double*)adj->y_out, lamJ,
                                                        dp, dp_assign, err_out, region, kSlabBlocks, B, st,
-                                                       table_build(h, h->built_vjp), &grid, h->opt.grid_vjp));
+                                                       table_build(h, h->built_vjp), &grid, h->opt.grid_vjp,
+                                                       &h->fk_launch));
                 kan::FinishJob& jb = h->jobs.j[h->njobs++];
                 jb.slab = region;
                 jb.err_slab = region + (int64_t)grid * (h->hlc[0].G + 1);   // (the region's row stride, not fk_moment_len)
@@ -453,7 +455,8 @@ kanode_status vjp_stage_t(kanode_handle* h, const T* p, const T* u, const kanode
             HIP_TRY(h, kan::launch_fk_vjp_stage_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), p, h->dtable(), cd, co,
                                                    (int)h->spec.nx, u, su, lam, sl, (double*)adj->y_out, lamJ, dp,
                                                    dp_assign, err_out, (double*)h->slab.ptr(), kSlabBlocks, B, st,
-                                                   table_build(h, h->built_vjp), nullptr, h->opt.grid_vjp));
+                                                   table_build(h, h->built_vjp), nullptr, h->opt.grid_vjp,
+                                                   &h->fk_launch));
             return KANODE_OK;
         }
     }

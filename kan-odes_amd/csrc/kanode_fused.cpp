@@ -38,7 +38,7 @@ kanode_status kanode_internal_fk_step_loop(kanode_handle* h, const void* p, cons
     }
     const auto [cd, co] = fk_lap(h);
     HIP_TRY(h, kan::launch_fk_step_pp_loop(h->hpc, h->hlc[0], h->dlc(), cd, co, (int)h->spec.nx, (const double*)p,
-                                           h->dtable(), *la, lq, batch, st, h->opt.grid_rhs));
+                                           h->dtable(), *la, lq, batch, st, h->opt.grid_rhs, &h->fk_launch));
     return KANODE_OK;
 }
 kanode_status kanode_internal_fk_step(kanode_handle* h, const void* p, const void* u, const void* k1,
@@ -55,7 +55,7 @@ kanode_status kanode_internal_fk_step(kanode_handle* h, const void* p, const voi
                                       (double*)u_new, a6x6, e7, q4x7, abstol, reltol,
                                       err_parts && nparts ? err_parts : (double*)h->slab.ptr(), kSlabBlocks, err_out, batch,
                                       (hipStream_t)stream, table_build(h, h->built_phi), h->opt.grid_rhs,
-                                      err_parts && nparts ? nparts : nullptr));
+                                      err_parts && nparts ? nparts : nullptr, &h->fk_launch));
     launched = true;
     return KANODE_OK;
 }
@@ -139,7 +139,7 @@ kanode_status kanode_internal_fk_adjoint_loop(kanode_handle* h, const void* p, c
                                               int64_t batch, void* stream) {
     const auto [cd, co] = fk_lap(h);
     HIP_TRY(h, kan::launch_fk_adjoint_loop(h->hpc, h->hlc[0], h->dlc(), h->dpc(), (const double*)p, h->dtable(), cd, co, (int)h->spec.nx, *la, batch, (hipStream_t)stream,
-                                           table_build(h, h->built_vjp)));
+                                           table_build(h, h->built_vjp), &h->fk_launch));
     return KANODE_OK;
 }
 kanode_status kanode_internal_fk_adjoint_step(kanode_handle* h, const void* p, kan::AdjStepArgs* a, void* const* km,
@@ -178,7 +178,7 @@ kanode_status kanode_internal_fk_adjoint_step(kanode_handle* h, const void* p, k
     HIP_TRY(h, kan::launch_fk_vjp_step_pp(h->hpc, h->hlc[0], h->dlc(), h->dpc(), (const double*)p, h->dtable(), cd, co,
                                           (int)h->spec.nx, *a, (double*)h->step_slab.ptr(), kSlabBlocks / 2, batch, &grid, st,
                                           table_build(h, h->built_vjp), h->opt.grid_vstep,
-                                          h->opt.vstep_rows != 0, &comb, &fused_fin));
+                                          h->opt.vstep_rows != 0, &comb, &fused_fin, &h->fk_launch));
     if (fused_fin) {   // μ_new, kμ_7 and the error terms are written by the step kernel itself
         *af->done = true;
         launched = true;

@@ -43,6 +43,7 @@ struct kanode_handle {
     kan::PPConst* dpc() const { return dpc_buf.as<kan::PPConst>(); }
     double* dtable() const { return dtable_buf.as<double>(); }
     HandleOptions opt;                // kanode_set_option (kanode_options.hpp)
+    kan::FkLaunchRec fk_launch{};     // the last table launch (kanode_last_fk_launch; family 0: none yet)
     double l1_penalty = 0.0;          // kanode_set_l1_penalty: λ of kanode_train_tsit5's loss term λ·Σ|p|
     std::vector<double> adj_steps;    // the last kanode_adjoint_tsit5's accepted step sizes (when recorded)
     kan::DevBuf fin_ctr;              // ADJ_FUSED_FINISH's two arrival counters (unsigned, zeroed at allocation)

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -48,6 +49,11 @@ class LayerCfg:
 
 
 _DT = {torch.float32: L.F32, torch.float64: L.F64}
+
+# kanode_last_fk_launch (include/kanode.h): out[0] indexes FK_FAMILIES
+FK_FAMILIES = ("none", "pair_short", "pair_long", "wave_rhs", "stage", "step", "step_loop", "vjp", "vjp_stage",
+               "adj_step_rows", "adj_step_wave", "adj_loop")
+FkLaunch = namedtuple("FkLaunch", "family np norm path gt ni256 chunk grid combine fused_finish")
 
 
 def _ptr(t: torch.Tensor | None):
@@ -555,6 +561,17 @@ class KanodeHandle:
         out = (C.c_int32 * 3)()
         L.check(L.lib().kanode_table_rejections(self._h, out), self._h, "kanode_table_rejections")
         return tuple(int(x) for x in out)
+
+    def last_fk_launch(self):
+        """The handle's last Fisher-KPP table launch (kanode_last_fk_launch): an FkLaunch of family (a name of
+        FK_FAMILIES), np, norm ("softsign", "tanh_fast", "runtime"), path ("rec", "rec_corr" or None), gt, ni256,
+        chunk, grid, combine, fused_finish."""
+        out = (C.c_int32 * 8)()
+        L.check(L.lib().kanode_last_fk_launch(self._h, out), self._h, "kanode_last_fk_launch")
+        v = [int(x) for x in out]
+        return FkLaunch(FK_FAMILIES[v[0]], v[1], {2: "softsign", 0: "tanh_fast", -1: "runtime"}[v[2]],
+                        {-1: None, 1: "rec", 2: "rec_corr"}[v[3]], v[4], bool(v[5] & 1), v[6], v[7], (v[5] >> 1) & 3,
+                        bool(v[5] & 8))
 
     def adjoint_step_sizes(self):
         """The accepted step sizes of the last adjoint_tsit5 (option record_adjoint_steps; else empty)."""

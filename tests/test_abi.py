@@ -26,7 +26,8 @@ def test_header_declares_the_boundary():
     names = declared_functions()
     for must in ("kanode_create", "kanode_destroy", "kanode_rhs", "kanode_vjp", "kanode_layer_forward",
                  "kanode_layer_vjp", "kanode_edge_activations", "kanode_last_error", "kanode_rhs_host",
-                 "kanode_vjp_host", "kanode_reserve", "kanode_knots", "kanode_param_length"):
+                 "kanode_vjp_host", "kanode_reserve", "kanode_knots", "kanode_param_length",
+                 "kanode_table_rejections", "kanode_last_fk_launch"):
         assert must in names
 
 
