@@ -579,7 +579,8 @@ kanode_status kanode_train_forward_tsit5(kanode_handle* h, void* p, void* m, voi
  * ran, even if some replica stopped; kanode_last_error then names the lowest stopped replica.
  *
  * Covered: exactly the shapes of kanode_train_supported / kanode_train_forward_supported, the former with
- * KANODE_OPT_TRAIN_ANY_CHAIN at 0 whatever the handle's value (replicas of a general chain are out of scope).
+ * KANODE_OPT_TRAIN_ANY_CHAIN at 0 whatever the handle's value (replicas of the other small chains are
+ * kanode_fit_ensemble_tsit5's, below).
  * Anything else: KANODE_ERR_UNSUPPORTED, nothing launched.  A capturing stream is refused (KANODE_ERR_CAPTURE). */
 kanode_status kanode_train_ensemble_tsit5(kanode_handle* h, int64_t n_replicas, void* p, void* m, void* v,
                                           const void* u0, int64_t batch, double t0, double tf, const double* saveat,
@@ -598,6 +599,41 @@ kanode_status kanode_train_forward_ensemble_tsit5(kanode_handle* h, int64_t n_re
                                                   double eps, const double* beta_t, int64_t n_iters, double* loss,
                                                   double* loss_test, void* grad, void* p_before, int64_t* counts,
                                                   int64_t* iters_done, int32_t* stop_reason, void* stream);
+
+/* --- ensemble training of every other small chain ----------------------------------------------
+ * kanode_fit_ensemble_tsit5 is kanode_train_ensemble_tsit5 for the chains that kanode_train_tsit5 covers only with
+ * KANODE_OPT_TRAIN_ANY_CHAIN on: a pruned [2 -> k -> 2], a [3 -> 6 -> 3] chain, three layers, [2 -> 10 -> 2] on up
+ * to 16 initial conditions.  One workgroup per replica runs kd_chain_train_wg_kernel's loop (its ensemble twin),
+ * and replica r computes, bit for bit, what kanode_train_tsit5 with the option on computes from the same p, m, v,
+ * eta, l1 and running powers.  The argument list, the per-replica arrays, the stop rule per replica and the return
+ * value are kanode_train_ensemble_tsit5's exactly (l1 is per replica; a parameter that is exactly zero under
+ * l1 > 0 makes that replica's loss NaN and stops it with KANODE_TRAIN_LOSS_NOT_FINITE, the others run on).
+ *
+ * Covered (kanode_fit_ensemble_supported): exactly the handles and batches that kanode_train_supported gains when
+ * KANODE_OPT_TRAIN_ANY_CHAIN goes from 0 to 1 -- fp64, batch <= 16, every layer within the one-workgroup kernels'
+ * widths.  The option is not read: calling this entry is the opt-in.  The Lotka-Volterra shape (one trajectory of
+ * the unpruned [2 -> 10 -> 2]) is NOT covered: it is kanode_train_ensemble_tsit5's, and the error text says so.
+ * Anything else: KANODE_ERR_UNSUPPORTED, nothing launched.  A capturing stream is refused (KANODE_ERR_CAPTURE).
+ *
+ * Launch groups.  Every replica has a private global block for its dense output (up to about 1.8 MB at 1024 steps
+ * of 32 state entries), so the handle's buffer is capped at 256 MiB: the call runs the replicas in consecutive
+ * groups of kanode_fit_ensemble_group(...) replicas (the last group smaller), each group one launch on the stream
+ * through the same code path; the caller sees one call and dense [n_replicas] outputs.  Usually that is one group.
+ * The cap bounds memory; it is not a tuning knob and cannot be set.  kanode_fit_ensemble_group returns the
+ * replicas per launch for a problem (the lengths of the saveat lists, the span and the solver options decide the
+ * dense-output capacity as for kanode_train_tsit5), at most 4096, or 0 where the problem is not covered or does not
+ * fit one workgroup's LDS. */
+int32_t kanode_fit_ensemble_supported(const kanode_handle* h, int64_t batch);
+int64_t kanode_fit_ensemble_group(const kanode_handle* h, int64_t batch, double t0, double tf, int64_t n_save,
+                                  int64_t n_save_test, const kanode_solver_options* opt);
+kanode_status kanode_fit_ensemble_tsit5(kanode_handle* h, int64_t n_replicas, void* p, void* m, void* v,
+                                        const void* u0, int64_t batch, double t0, double tf, const double* saveat,
+                                        int64_t n_save, const void* target, double tf_test, const double* saveat_test,
+                                        int64_t n_save_test, const void* target_test,
+                                        const kanode_solver_options* opt, const double* eta, const double* l1,
+                                        double beta1, double beta2, double eps, const double* beta_t, int64_t n_iters,
+                                        double* loss, double* loss_test, void* grad, void* p_before, int64_t* counts,
+                                        int64_t* iters_done, int32_t* stop_reason, void* stream);
 
 /* --- ensemble solve: one problem at n_replicas parameter vectors in ONE launch -----------------
  * The forward solve of kanode_solve_tsit5 (control = auto, no dense output) at every row of p [n_replicas][P], one

@@ -567,6 +567,28 @@ function train_ensemble_tsit5!(h::Handle, R::Integer, p::Ptr{Cvoid}, m::Ptr{Cvoi
                                η, l1v, β, ϵ, βp, test, loss_test, grad, p_before, counts, opt, stream)
 end
 
+# the ensemble of every other small chain (kanode_fit_ensemble_tsit5): a pruned [2,k,2], [3,6,3], three layers, up to
+# 16 initial conditions; never the Lotka-Volterra shape, which train_ensemble_tsit5! keeps
+fit_ensemble_supported(h::Handle, B::Integer) =
+    ccall(sym(:kanode_fit_ensemble_supported), Int32, (Ptr{Cvoid}, Int64), h.ptr, B) == 1
+
+"""fit_ensemble_tsit5!(h, R, p, m, v, u0, B, tspan, saveat, target, n_iters, loss; η, l1, β, ϵ, βp, test, loss_test,
+grad, p_before, counts, opt) -> (iters_done, stop_reason), vectors of R: train_ensemble_tsit5! for the small chains
+train_tsit5! covers only after train_any_chain! (the option is not read: this call is the opt-in), at B trajectories.
+Replica r equals train_tsit5! on that handle, bit for bit.  The arguments are train_ensemble_tsit5!'s."""
+function fit_ensemble_tsit5!(h::Handle, R::Integer, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cvoid}, u0::Ptr{Cvoid},
+                             B::Integer, tspan, saveat::Vector{Float64}, target::Ptr{Cvoid}, n_iters::Integer,
+                             loss::Ptr{Cvoid}; η = 1e-3, l1 = nothing, β = (0.9, 0.999), ϵ::Real = 1e-8, βp = nothing,
+                             test = nothing, loss_test::Ptr{Cvoid} = C_NULL, grad::Ptr{Cvoid} = C_NULL,
+                             p_before::Ptr{Cvoid} = C_NULL, counts::Ptr{Cvoid} = C_NULL,
+                             opt::SolverOptions = default_options(), stream::Ptr{Cvoid} = C_NULL)
+    fit_ensemble_supported(h, B) ||
+        throw(ArgumentError("fit_ensemble_tsit5!: not covered for this handle (the Lotka-Volterra shape: train_ensemble_tsit5!)"))
+    l1v = l1 isa Real ? fill(Float64(l1), R) : l1
+    return train_ensemble_call(:kanode_fit_ensemble_tsit5, h, R, p, m, v, u0, B, tspan, saveat, target, n_iters, loss,
+                               η, l1v, β, ϵ, βp, test, loss_test, grad, p_before, counts, opt, stream)
+end
+
 """train_forward_ensemble_tsit5!(h, R, p, m, v, u0, B, tspan, saveat, target, n_iters, loss; ...) ->
 (iters_done, stop_reason): train_forward_tsit5! on R replicas at once (no L1 term)."""
 function train_forward_ensemble_tsit5!(h::Handle, R::Integer, p::Ptr{Cvoid}, m::Ptr{Cvoid}, v::Ptr{Cvoid},

@@ -5,7 +5,7 @@
 //     out [R][2] int64 | rec [R][rec_stride bytes] | args [R] | meta | 64 spare bytes
 // every block at a multiple of 64 bytes.  out[r] are replica r's status words (iterations done, stop reason), rec
 // its private block (the LV loop's global dense output, the Fisher-KPP loop's accumulators; rec_bytes = 0 where the
-// kernel keeps them in LDS), args the structs the workgroups read, meta the ONE copy of what all replicas share
+// kernel keeps them in LDS; the general small-chain loop's dense output and cotangent rows, always there), args the structs the workgroups read, meta the ONE copy of what all replicas share
 // (saveat lists, jump groups).
 #pragma once
 #include <stddef.h>
@@ -28,6 +28,27 @@ inline EnsembleLayout ensemble_layout(int64_t R, size_t rec_bytes, size_t arg_by
 // the bytes the buffer needs for this layout and a meta block of meta_bytes
 inline size_t ensemble_bytes(const EnsembleLayout& L, size_t meta_bytes) { return L.off_meta + meta_bytes + 64; }
 
+// The replicas of one launch where the private blocks are large (kanode_fit_ensemble_tsit5: a dense-output block of
+// up to ~1.8 MB per replica): the largest G <= R whose buffer, laid out as above, stays within `budget` bytes; 0
+// when not even one replica does.  The C entry runs R replicas in consecutive groups of G (the last one smaller),
+// one launch each.  A cap on the memory a handle holds, not a tuning knob: a group that fits is never split.
+constexpr size_t kEnsembleBudget = (size_t)256 << 20;
+inline int64_t ensemble_group(int64_t R, size_t rec_bytes, size_t arg_bytes, size_t meta_bytes, size_t budget) {
+    int64_t lo = 0, hi = R < 0 ? 0 : R;   // (the buffer's size grows with the replica count)
+    while (lo < hi) {
+        const int64_t mid = lo + (hi - lo + 1) / 2;
+        if (ensemble_bytes(ensemble_layout(mid, rec_bytes, arg_bytes), meta_bytes) <= budget) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+// an upper bound of the chain loops' meta block (kanode_train.cpp: saveat, saveat_test, at most n_save + 1 stops as
+// doubles; at most n_save + 3 offsets and n_save rows as int32), so that the group size depends on the list
+// lengths alone
+inline size_t ensemble_meta_bound(int64_t n_save, int64_t n_save_test) {
+    return (size_t)(2 * n_save + n_save_test + 1) * sizeof(double) + (size_t)(2 * n_save + 3) * sizeof(int32_t);
+}
+
 // What differs between the replicas, as the C entry points receive it: p, m, v [R][P] and the outputs with their
 // leading replica dimension are device arrays (the record pointers nullable), eta [R], l1 [R] (nullable: all zero)
 // and beta_t [R][2] host arrays.
@@ -38,6 +59,25 @@ struct EnsembleReplicas {
     double *loss, *loss_test, *grad, *p_before;
     int64_t* counts;
 };
+
+// replicas g0 .. g0 + G - 1 (cut at e.R) of e as an ensemble of their own: one launch group of a call
+inline EnsembleReplicas ensemble_slice(const EnsembleReplicas& e, int64_t g0, int64_t G) {
+    const size_t q = (size_t)g0, P = (size_t)e.P, K = (size_t)e.n_iters;
+    EnsembleReplicas s = e;
+    s.R = e.R - g0 < G ? e.R - g0 : G;
+    s.p += q * P;
+    s.m += q * P;
+    s.v += q * P;
+    s.eta += q;
+    if (s.l1) s.l1 += q;
+    s.beta_t += 2 * q;
+    s.loss += q * K;
+    if (s.loss_test) s.loss_test += q * K;
+    if (s.grad) s.grad += q * K * P;
+    if (s.p_before) s.p_before += q * K * P;
+    if (s.counts) s.counts += q * K * 4;
+    return s;
+}
 
 // args[r] = shared with replica r's own fields set; base is the DEVICE address of the buffer laid out by L
 // (only offsets are formed from it, nothing is read through it).  Args: kan::ChainTrainArgs.

@@ -556,6 +556,11 @@ constexpr int64_t kTrainMaxReplicas = 4096;
 hipError_t launch_kd_chain_train_ensemble(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P,
                                           const ChainTrainArgs& a, const ChainTrainArgs* args, int64_t n_rep,
                                           hipStream_t st);
+// launch_kd_chain_train_wg's ensemble twin (kd_chain_train_wg_ens_kernel; kanode_fit_ensemble_tsit5): the same
+// shapes, refusals, block and LDS carve, a grid of n_rep; every struct of args has its own private block in rec
+hipError_t launch_kd_chain_train_wg_ensemble(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P,
+                                             int64_t B, bool wide, const ChainTrainArgs& a, const ChainTrainArgs* args,
+                                             int64_t n_rep, hipStream_t st);
 // K whole training iterations of a small Fisher-KPP field on the forward-mode gradient in ONE launch
 // (fk_small_train_kernel, kan_small_train.hip; Fisher-KPP_Source.jl:194-213): per iteration the tables at p_it
 // (pp_build_block, with tab), the Dual solve of fk_small_fsens_kernel with loss[it] and the gradient accumulated at

@@ -1,6 +1,8 @@
 // kan_train_wg.hip — K whole training iterations of a small chain in ONE launch (gfx950), for every shape the
 // one-workgroup forward and adjoint cover that kan_train.hip's Lotka-Volterra kernel does not: a pruned [2,k,2],
-// a [3,6,3] chain, three layers, up to kChainSolveMaxBatch trajectories (KANODE_OPT_TRAIN_ANY_CHAIN).
+// a [3,6,3] chain, three layers, up to kChainSolveMaxBatch trajectories (KANODE_OPT_TRAIN_ANY_CHAIN), and its ensemble
+// twin, R such loops in one launch, one workgroup each (kanode_fit_ensemble_tsit5).  The loop's text is
+// kan_train_wg_body.inc, included into both kernels.
 //
 // The loop is LV_driver_KANODE.jl:279-291, as in kan_train.hip; here every phase runs on the whole workgroup, with
 // the device functions of the two-launch path (kan_onewg.hpp on the model classes of kan_col.hip).  Per iteration it:
@@ -258,99 +260,21 @@ __device__ __noinline__ void wg_adam(const ChainTrainArgs& a, const TrainWgPtrs&
 template <int FN, int PATH, class FS, int ADJ, int WN>
 __global__ void __launch_bounds__(kChainBlock)
 kd_chain_train_wg_kernel(const LayerConst* __restrict__ lcs, int nl, int P, ChainTrainArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char tw_raw[];
-    __shared__ double red[kChainBlock / kWave];
-    __shared__ int64_t fo[12];
-    __shared__ double lossv;
-    const int64_t n = a.N * a.B;
-    const int64_t work = ADJ == kWgWide ? (int64_t)WideModel<double, WN>::kEnd : (int64_t)(blockDim.x / kChainDim) * P;
-    const TrainWgCarve c = train_wg_carve(P, work, a.cap, a.n_save, a.n_save_test, n, a.dl_lds, a.stage_rec);
-    double* const base = reinterpret_cast<double*>(tw_raw + nl * sizeof(LayerConst));
-    TrainWgPtrs L;
-    L.lcl = (KAN_LDS const LayerConst*)reinterpret_cast<const LayerConst*>(tw_raw);
-    L.ps = (KAN_LDS double*)(base + c.ps);
-    L.work = (KAN_LDS double*)(base + c.work);
-    L.mu = (KAN_LDS double*)(base + c.mu);
-    L.km = (KAN_LDS double*)(base + c.km);
-    L.gl = (KAN_LDS double*)(base + c.gl);
-    L.tsl = (KAN_LDS double*)(base + c.tsl);
-    L.dtsl = (KAN_LDS double*)(base + c.dtsl);
-    L.sv = (KAN_LDS double*)(base + c.sv);
-    L.svt = (KAN_LDS double*)(base + c.svt);
-    L.rec = a.rec;
-    L.rk1 = a.rec + a.cap * 7 * n;
-    L.dl = a.dl_lds ? base + c.dl : L.rk1 + n;
-    L.ust = a.dl_lds ? base + c.ust : L.rk1 + n + a.n_save * n;
-    L.recl = (KAN_LDS double*)(base + c.recl);
-    L.red = (KAN_LDS double*)red;
-    L.fo = (KAN_LDS int64_t*)fo;
-    L.lossv = (KAN_LDS double*)&lossv;
-    L.nl = nl;
-    L.P = P;
-    {
-        const int nw = nl * (int)(sizeof(LayerConst) / sizeof(int32_t));
-        const int32_t* src = reinterpret_cast<const int32_t*>(lcs);
-        int32_t* dst = reinterpret_cast<int32_t*>(tw_raw);
-        stage_chain_consts(dst, src, nw, base + c.ps, a.p, P);
-        for (int64_t i = threadIdx.x; i < a.n_save; i += blockDim.x) L.sv[i] = a.saveat[i];
-        for (int64_t i = threadIdx.x; i < a.n_save_test; i += blockDim.x) L.svt[i] = a.saveat_test[i];
-        if (threadIdx.x < 12) fo[threadIdx.x] = 0;
-    }
-    KAN_EXP_TABLE_LDS(tab);   // (its barrier also publishes the constants, ps, the saveat lists and fo)
-    L.tab = (KAN_LDS const double*)tab;
-    const bool has_test = a.n_save_test > 0 && a.loss_test != nullptr;
-    double bp1 = a.bp1, bp2 = a.bp2;
-    int64_t done = 0;
-    int reason = kTrainOk;
-    for (int64_t it = 0; it <= a.n_iters; ++it) {
-        const bool tst = has_test && it > 0;
-        if (it == a.n_iters && !tst) break;
-        // ---- A: the solves at p_it, the loss and its cotangent ----
-        if (it < a.n_iters) {
-            wg_forward<FN, PATH, FS>(a, L, false);
-            __syncthreads();   // u_save, the dense output, ts / dts and the counters, to every wave
-            if (fo[3] == 0) wg_loss(a, L, it);
-        }
-        if (tst) {
-            wg_forward<FN, PATH, FS>(a, L, true);
-            __syncthreads();
-            wg_test_loss(a, L, it);
-        }
-        __syncthreads();
-        if (tst && fo[7] != 0) {
-            reason = kTrainTestMaxiters;
-            break;
-        }
-        if (it == a.n_iters) break;
-        if (fo[3] != 0) {
-            reason = fo[3] == 2 ? kTrainDenseCapacity : kTrainForwardMaxiters;
-            break;
-        }
-        if (!(::fabs(lossv) <= 1.7976931348623157e308)) {
-            reason = kTrainLossNotFinite;
-            break;
-        }
-        // ---- B: the InterpolatingAdjoint from the dense output just written ----
-        wg_adjoint<ADJ, WN, FN, PATH, FS>(a, L);
-        __syncthreads();   // the gradient and the adjoint's counters
-        if (fo[11] != 0) {
-            reason = kTrainAdjointMaxiters;
-            break;
-        }
-        // ---- C: records and Adam ----
-        wg_adam(a, L, it, bp1, bp2);
-        __syncthreads();   // p_{it+1} in LDS; every wave is done with dl, the gradient and the counters
-        {   // the rounded products Python's `bp *= β` forms
-#pragma clang fp contract(off)
-            bp1 = bp1 * a.ab1;
-            bp2 = bp2 * a.ab2;
-        }
-        done = it + 1;
-    }
-    if (threadIdx.x == 0) {
-        a.out[0] = done;
-        a.out[1] = reason;
-    }
+#include "kan_train_wg_body.inc"
+}
+
+// The ensemble twin (kanode_fit_ensemble_tsit5): workgroup r runs the same loop on its copy of args[r] (its own p, m,
+// v, Adam scalars, λ, records, private global block and status words; the problem, the jump groups, cap, dl_lds and
+// stage_rec are the same in every struct, so the LDS carve is every workgroup's alike).  The copy is made once, ahead
+// of the body's first barrier, from a uniform read-only address: scalar loads.  The block index is used for nothing
+// else: the workgroups share nothing they write and never wait for each other, and one that stops writes its own two
+// status words and returns.
+template <int FN, int PATH, class FS, int ADJ, int WN>
+__global__ void __launch_bounds__(kChainBlock)
+kd_chain_train_wg_ens_kernel(const LayerConst* __restrict__ lcs, int nl, int P,
+                             const ChainTrainArgs* __restrict__ args) {
+    const ChainTrainArgs a = args[blockIdx.x];
+#include "kan_train_wg_body.inc"
 }
 
 // The adjoint's model, block and staging: where the forward fits the one-workgroup solve (at any step count: it keeps
@@ -394,10 +318,14 @@ bool chain_train_wg_supported(const LayerConst* hlcs, int nl, int64_t P, int64_t
     return chain_train_wg_lds(hlcs, nl, P, B, wide, 1, 1, 0, nullptr, nullptr) != 0;
 }
 
-hipError_t launch_kd_chain_train_wg(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P, int64_t B,
-                                    bool wide, const ChainTrainArgs& a, hipStream_t st) {
+// args == nullptr: the single-replica kernel on `a`; else the ensemble kernel, one workgroup per struct of the device
+// array args [n_rep] (a: the host copy of any one of them -- they agree in every field read here; each has a private
+// block of its own in rec)
+static hipError_t launch_train_wg(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P, int64_t B,
+                                  bool wide, const ChainTrainArgs& a, const ChainTrainArgs* args, int64_t n_rep,
+                                  hipStream_t st) {
     if (!chain_train_wg_supported(hlcs, nl, P, B, sizeof(double), wide) || a.n_iters < 1 || a.B != B ||
-        a.N != hlcs[0].I || !a.rec)
+        a.N != hlcs[0].I || !a.rec || (args && (n_rep < 1 || n_rep > kTrainMaxReplicas)))
         return hipErrorNotSupported;
     int dl = 0, sr = 0;
     const size_t lds = chain_train_wg_lds(hlcs, nl, P, B, wide, a.cap, a.n_save, a.n_save_test, &dl, &sr);
@@ -407,11 +335,16 @@ hipError_t launch_kd_chain_train_wg(const LayerConst* hlcs, int nl, const LayerC
     const LayerConst& h = hlcs[0];
 #define KAN_TWG_GO(FN, PATH, FS, ADJ, WN)                                                                            \
     do {                                                                                                            \
-        const void* fn = reinterpret_cast<const void*>(&kd_chain_train_wg_kernel<FN, PATH, FS, ADJ, WN>);           \
+        const void* fn = args ? reinterpret_cast<const void*>(&kd_chain_train_wg_ens_kernel<FN, PATH, FS, ADJ, WN>) \
+                              : reinterpret_cast<const void*>(&kd_chain_train_wg_kernel<FN, PATH, FS, ADJ, WN>);    \
         const hipError_t e = ensure_dynamic_lds(fn, lds);                                                           \
         if (e != hipSuccess) return e;                                                                              \
-        hipLaunchKernelGGL((kd_chain_train_wg_kernel<FN, PATH, FS, ADJ, WN>), dim3(1), dim3(threads), lds, st, lcs, \
-                           nl, (int)P, a);                                                                          \
+        if (args)                                                                                                   \
+            hipLaunchKernelGGL((kd_chain_train_wg_ens_kernel<FN, PATH, FS, ADJ, WN>), dim3((unsigned)n_rep),        \
+                               dim3(threads), lds, st, lcs, nl, (int)P, args);                                      \
+        else                                                                                                        \
+            hipLaunchKernelGGL((kd_chain_train_wg_kernel<FN, PATH, FS, ADJ, WN>), dim3(1), dim3(threads), lds, st,  \
+                               lcs, nl, (int)P, a);                                                                 \
     } while (0)
     // the forward's specialisation is the ladder's rung.  Under WideModel the rung is paired with the adjoint's
     // normalizer and only the six combinations a handle reaches exist (a [2,10,2] G = 5 chain on the exact
@@ -433,6 +366,17 @@ hipError_t launch_kd_chain_train_wg(const LayerConst* hlcs, int nl, const LayerC
     }
 #undef KAN_TWG_GO
     return hipGetLastError();
+}
+
+hipError_t launch_kd_chain_train_wg(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P, int64_t B,
+                                    bool wide, const ChainTrainArgs& a, hipStream_t st) {
+    return launch_train_wg(hlcs, nl, lcs, P, B, wide, a, nullptr, 1, st);
+}
+
+hipError_t launch_kd_chain_train_wg_ensemble(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P,
+                                             int64_t B, bool wide, const ChainTrainArgs& a, const ChainTrainArgs* args,
+                                             int64_t n_rep, hipStream_t st) {
+    return args ? launch_train_wg(hlcs, nl, lcs, P, B, wide, a, args, n_rep, st) : hipErrorNotSupported;
 }
 
 #undef KAN_LDS

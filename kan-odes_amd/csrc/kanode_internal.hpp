@@ -181,10 +181,21 @@ kanode_status kanode_internal_fk_fsens(kanode_handle* h, const void* p, const vo
 // dense-output block, the per-replica argument structs formed from *a, and ONE copy of meta; res is [R][2].
 bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch);
 // (KANODE_OPT_TRAIN_ANY_CHAIN: a chain that is not the Lotka-Volterra loop's runs kd_chain_train_wg_kernel; with ens
-// it is refused, nothing launched)
+// it is refused, nothing launched: those ensembles are kanode_internal_chain_fit_ensemble's)
 kanode_status kanode_internal_chain_train(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
                                           const kan::EnsembleReplicas* ens, const std::vector<char>& meta, int64_t* res,
                                           void* stream);
+// kanode_fit_ensemble_tsit5: ens->R replicas of a small chain that is not the Lotka-Volterra loop's
+// (kd_chain_train_wg_ens_kernel), whatever KANODE_OPT_TRAIN_ANY_CHAIN says.  _ok: the shapes covered; _group: the
+// replicas of one launch for this problem (kan_ensemble.hpp's ensemble_group at the 256 MiB budget; 0: not covered or
+// no fit in LDS); the call runs consecutive groups of that size, one launch each, and fills res [R][2] densely.
+bool kanode_internal_fit_ensemble_ok(const kanode_handle* h, int64_t batch);
+bool kanode_internal_chain_train_lv_ok(const kanode_handle* h, int64_t batch);   // (the Lotka-Volterra loop's shape)
+int64_t kanode_internal_fit_ensemble_group(const kanode_handle* h, int64_t batch, bool adaptive, double t0, double tf,
+                                           double dt, int64_t n_save, int64_t n_save_test);
+kanode_status kanode_internal_chain_fit_ensemble(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
+                                                 const kan::EnsembleReplicas* ens, const std::vector<char>& meta,
+                                                 int64_t* res, void* stream);
 // the device-resident Fisher-KPP training loop on the forward-mode gradient (fk_small_train_kernel,
 // kanode_train_forward_tsit5): whether the handle takes it at this batch (with_test: with the logged-loss solve),
 // and one launch.  meta = saveat [n_save] | saveat_test [n_save_test] (doubles), kept on the handle with the two

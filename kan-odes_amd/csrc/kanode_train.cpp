@@ -82,8 +82,10 @@ extern "C" int32_t kanode_train_supported(const kanode_handle* h, int64_t batch)
 // The two device-resident loops share everything but the kernel: `forward` = the Fisher-KPP loop on the forward-mode
 // gradient (kanode_train_forward_tsit5), else the Lotka-Volterra loop on the InterpolatingAdjoint (kanode_train_tsit5).
 // ens: the ensemble entries' per-replica arrays (p, m, v and the outputs are then [R][..], iters_done and stop_reason
-// [R]; eta, beta1_t, beta2_t and the handle's L1 penalty are not read), else null.
-static kanode_status train_tsit5_impl(bool forward, const kan::EnsembleReplicas* ens, kanode_handle* h, void* p, void* m,
+// [R]; eta, beta1_t, beta2_t and the handle's L1 penalty are not read), else null.  kLoopFit (with ens alone): the
+// adjoint loop on the small chains that are not the Lotka-Volterra shape (kanode_fit_ensemble_tsit5).
+enum TrainLoop : int { kLoopAdjoint = 0, kLoopForward = 1, kLoopFit = 2 };
+static kanode_status train_tsit5_impl(TrainLoop loop, const kan::EnsembleReplicas* ens, kanode_handle* h, void* p, void* m,
                                             void* v, const void* u0, int64_t batch,
                                             double t0, double tf, const double* saveat, int64_t n_save,
                                             const void* target, double tf_test, const double* saveat_test,
@@ -93,7 +95,10 @@ static kanode_status train_tsit5_impl(bool forward, const kan::EnsembleReplicas*
                                             double* loss_test, void* grad, void* p_before, int64_t* counts,
                                             int64_t* iters_done, int32_t* stop_reason, void* stream) {
     SOLVE_TRY(kanode_internal_check(h));
-    const std::string name = std::string(forward ? "kanode_train_forward" : "kanode_train") + (ens ? "_ensemble_tsit5" : "_tsit5");
+    const bool forward = loop == kLoopForward, fit = loop == kLoopFit;
+    const std::string name = fit ? std::string("kanode_fit_ensemble_tsit5")
+                                 : std::string(forward ? "kanode_train_forward" : "kanode_train") + (ens ? "_ensemble_tsit5" : "_tsit5");
+    if (fit && !ens) return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": an ensemble entry");
     if (ens && (ens->R < 1 || ens->R > kan::kTrainMaxReplicas))
         return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": 1 <= n_replicas <= 4096");
     const int64_t R = ens ? ens->R : 1;
@@ -103,7 +108,17 @@ static kanode_status train_tsit5_impl(bool forward, const kan::EnsembleReplicas*
     }
     const kanode_solver_options o = resolved(opt);
     SOLVE_TRY(check_opts(h, o));
-    if (!forward && (batch < 1 || !kanode_internal_chain_train_ok(h, batch)))
+    if (fit && (batch < 1 || !kanode_internal_fit_ensemble_ok(h, batch))) {
+        // (the Lotka-Volterra shape has an ensemble entry of its own, whatever KANODE_OPT_TRAIN_ANY_CHAIN says)
+        const bool lv = batch >= 1 && kanode_internal_chain_train_lv_ok(h, batch);
+        return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
+                                    name + (lv ? ": not supported (one Lotka-Volterra trajectory per replica is "
+                                                 "kanode_train_ensemble_tsit5's shape: call that entry)"
+                                               : ": not supported (covered: every fp64 chain of the one-workgroup solve "
+                                                 "and adjoint at batch <= 16 that is not the Lotka-Volterra shape, "
+                                                 "fused_solve on)"));
+    }
+    if (!fit && !forward && (batch < 1 || !kanode_internal_chain_train_ok(h, batch)))
         return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
                                     name + ": not supported (covered: one trajectory of an fp64 chain [2,10,2], "
                                     "G = 5, rbf, base activations, tanh_fast / softsign, fused_solve and chain_wide on; "
@@ -195,6 +210,7 @@ static kanode_status train_tsit5_impl(bool forward, const kan::EnsembleReplicas*
     a.act_reg = forward || ens ? 0.0 : kanode_get_l1_penalty(h);   // (an ensemble's: per replica, from ens->l1)
     std::vector<int64_t> res(2 * (size_t)R, 0);
     if (forward) SOLVE_TRY(kanode_internal_fk_train(h, batch, &a, ens, meta, res.data(), st));
+    else if (fit) SOLVE_TRY(kanode_internal_chain_fit_ensemble(h, batch, &a, ens, meta, res.data(), st));
     else SOLVE_TRY(kanode_internal_chain_train(h, batch, &a, ens, meta, res.data(), st));
     static const char* const why[] = {"", "forward Tsit5: maxiters reached", "forward dense-output capacity exceeded "
                                       "(KANODE_OPT_FUSED_SOLVE_CAP)", "adjoint Tsit5: maxiters reached",
@@ -225,7 +241,7 @@ extern "C" kanode_status kanode_train_tsit5(kanode_handle* h, void* p, void* m, 
                                             double eps, double beta1_t, double beta2_t, int64_t n_iters, double* loss,
                                             double* loss_test, void* grad, void* p_before, int64_t* counts,
                                             int64_t* iters_done, int32_t* stop_reason, void* stream) {
-    return train_tsit5_impl(false, nullptr, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+    return train_tsit5_impl(kLoopAdjoint, nullptr, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
                             n_save_test, target_test, opt, eta, beta1, beta2, eps, beta1_t, beta2_t, n_iters, loss,
                             loss_test, grad, p_before, counts, iters_done, stop_reason, stream);
 }
@@ -244,13 +260,13 @@ extern "C" kanode_status kanode_train_forward_tsit5(kanode_handle* h, void* p, v
                                                     double beta2_t, int64_t n_iters, double* loss, double* loss_test,
                                                     void* grad, void* p_before, int64_t* counts, int64_t* iters_done,
                                                     int32_t* stop_reason, void* stream) {
-    return train_tsit5_impl(true, nullptr, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+    return train_tsit5_impl(kLoopForward, nullptr, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
                             n_save_test, target_test, opt, eta, beta1, beta2, eps, beta1_t, beta2_t, n_iters, loss,
                             loss_test, grad, p_before, counts, iters_done, stop_reason, stream);
 }
 
 // ---- the ensemble entries: n_replicas independent loops in one launch, one workgroup each ----
-static kanode_status train_ensemble(bool forward, kanode_handle* h, int64_t n_replicas, void* p, void* m, void* v,
+static kanode_status train_ensemble(TrainLoop loop, kanode_handle* h, int64_t n_replicas, void* p, void* m, void* v,
                                     const void* u0, int64_t batch, double t0, double tf, const double* saveat,
                                     int64_t n_save, const void* target, double tf_test, const double* saveat_test,
                                     int64_t n_save_test, const void* target_test, const kanode_solver_options* opt,
@@ -273,7 +289,7 @@ static kanode_status train_ensemble(bool forward, kanode_handle* h, int64_t n_re
     e.grad = (double*)grad;
     e.p_before = (double*)p_before;
     e.counts = counts;
-    return train_tsit5_impl(forward, &e, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+    return train_tsit5_impl(loop, &e, h, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
                             n_save_test, target_test, opt, 0.0, beta1, beta2, eps, 0.0, 0.0, n_iters, loss, loss_test,
                             grad, p_before, counts, iters_done, stop_reason, stream);
 }
@@ -287,7 +303,7 @@ extern "C" kanode_status kanode_train_ensemble_tsit5(kanode_handle* h, int64_t n
                                                      double eps, const double* beta_t, int64_t n_iters, double* loss,
                                                      double* loss_test, void* grad, void* p_before, int64_t* counts,
                                                      int64_t* iters_done, int32_t* stop_reason, void* stream) {
-    return train_ensemble(false, h, n_replicas, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+    return train_ensemble(kLoopAdjoint, h, n_replicas, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
                           n_save_test, target_test, opt, eta, l1, beta1, beta2, eps, beta_t, n_iters, loss, loss_test,
                           grad, p_before, counts, iters_done, stop_reason, stream);
 }
@@ -298,7 +314,33 @@ extern "C" kanode_status kanode_train_forward_ensemble_tsit5(
     int64_t n_save_test, const void* target_test, const kanode_solver_options* opt, const double* eta, const double* l1,
     double beta1, double beta2, double eps, const double* beta_t, int64_t n_iters, double* loss, double* loss_test,
     void* grad, void* p_before, int64_t* counts, int64_t* iters_done, int32_t* stop_reason, void* stream) {
-    return train_ensemble(true, h, n_replicas, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
+    return train_ensemble(kLoopForward, h, n_replicas, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test, saveat_test,
                           n_save_test, target_test, opt, eta, l1, beta1, beta2, eps, beta_t, n_iters, loss, loss_test,
                           grad, p_before, counts, iters_done, stop_reason, stream);
+}
+
+// ---- ensembles of the other small chains (kd_chain_train_wg_ens_kernel): the entry itself is the opt-in ----
+extern "C" int32_t kanode_fit_ensemble_supported(const kanode_handle* h, int64_t batch) {
+    return h && batch >= 1 && kanode_internal_fit_ensemble_ok(h, batch) ? 1 : 0;
+}
+
+extern "C" int64_t kanode_fit_ensemble_group(const kanode_handle* h, int64_t batch, double t0, double tf, int64_t n_save,
+                                             int64_t n_save_test, const kanode_solver_options* opt) {
+    if (!h) return 0;
+    const kanode_solver_options o = resolved(opt);
+    return kanode_internal_fit_ensemble_group(h, batch, o.adaptive != 0, t0, tf, o.dt, n_save, n_save_test);
+}
+
+extern "C" kanode_status kanode_fit_ensemble_tsit5(kanode_handle* h, int64_t n_replicas, void* p, void* m, void* v,
+                                                   const void* u0, int64_t batch, double t0, double tf,
+                                                   const double* saveat, int64_t n_save, const void* target,
+                                                   double tf_test, const double* saveat_test, int64_t n_save_test,
+                                                   const void* target_test, const kanode_solver_options* opt,
+                                                   const double* eta, const double* l1, double beta1, double beta2,
+                                                   double eps, const double* beta_t, int64_t n_iters, double* loss,
+                                                   double* loss_test, void* grad, void* p_before, int64_t* counts,
+                                                   int64_t* iters_done, int32_t* stop_reason, void* stream) {
+    return train_ensemble(kLoopFit, h, n_replicas, p, m, v, u0, batch, t0, tf, saveat, n_save, target, tf_test,
+                          saveat_test, n_save_test, target_test, opt, eta, l1, beta1, beta2, eps, beta_t, n_iters, loss,
+                          loss_test, grad, p_before, counts, iters_done, stop_reason, stream);
 }

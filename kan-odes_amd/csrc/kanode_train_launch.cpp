@@ -14,12 +14,17 @@ static bool chain_train_lv_ok(const kanode_handle* h, int64_t batch) {
     return h->spec.rhs_kind == KANODE_RHS_CHAIN && kanode_internal_chain_tsit5_ok(h, batch) &&
            kan::chain_train_supported(h->hlc, h->n_layers, h->P, batch, h->esize, h->opt.chain_wide);
 }
-// with the option on: every other small fp64 chain (kd_chain_train_wg_kernel)
-static bool chain_train_wg_ok(const kanode_handle* h, int64_t batch) {
-    return h->opt.train_any_chain && h->spec.dtype == KANODE_F64 && h->spec.rhs_kind == KANODE_RHS_CHAIN &&
+// every other small fp64 chain (kd_chain_train_wg_kernel): what kanode_train_tsit5 gains with the option on, and what
+// kanode_fit_ensemble_tsit5 covers whatever the option says (never the Lotka-Volterra loop's shape)
+bool kanode_internal_fit_ensemble_ok(const kanode_handle* h, int64_t batch) {
+    return h->spec.dtype == KANODE_F64 && h->spec.rhs_kind == KANODE_RHS_CHAIN &&
            kanode_internal_chain_tsit5_ok(h, batch) &&
            kan::chain_train_wg_supported(h->hlc, h->n_layers, h->P, batch, h->esize, h->opt.chain_wide);
 }
+static bool chain_train_wg_ok(const kanode_handle* h, int64_t batch) {
+    return h->opt.train_any_chain && kanode_internal_fit_ensemble_ok(h, batch);
+}
+bool kanode_internal_chain_train_lv_ok(const kanode_handle* h, int64_t batch) { return chain_train_lv_ok(h, batch); }
 bool kanode_internal_chain_train_ok(const kanode_handle* h, int64_t batch) {
     return chain_train_lv_ok(h, batch) || chain_train_wg_ok(h, batch);
 }
@@ -92,12 +97,18 @@ static kanode_status train_launch(kanode_handle* h, const char* what, kan::Chain
 // kanode_train_tsit5 on a chain that is not the Lotka-Volterra loop's (KANODE_OPT_TRAIN_ANY_CHAIN): the capacity by
 // the same rules (the option, a fixed-step solve's own count, else the most steps that leave u_save / dl in LDS, at
 // least 64, else kChainAdjointMaxSteps or what fits), the private block sized for it
-static kanode_status chain_train_wg(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
-                                    const std::vector<char>& meta, int64_t* res, hipStream_t st) {
-    const char* what = "kanode_train_tsit5";
+// (one rule for a single run and for every replica of an ensemble: the same cap, dl_lds and stage_rec, so the same
+// LDS carve)
+struct TrainWgFit {
+    int64_t cap;
+    int dl_lds, stage_rec;
+    size_t rec_bytes;   // the private global block (ChainTrainArgs::rec), a multiple of 64 bytes
+};
+static bool chain_train_wg_fit(const kanode_handle* h, int64_t batch, bool adaptive, double t0, double tf, double dt,
+                               int64_t n_save, int64_t n_save_test, TrainWgFit& f) {
     const bool wide = h->opt.chain_wide;
     auto lds = [&](int64_t cap, int* dl, int* sr) {
-        return kan::chain_train_wg_lds(h->hlc, h->n_layers, h->P, batch, wide, cap, a->n_save, a->n_save_test, dl, sr);
+        return kan::chain_train_wg_lds(h->hlc, h->n_layers, h->P, batch, wide, cap, n_save, n_save_test, dl, sr);
     };
     int64_t cap = std::min<int64_t>(h->opt.fused_solve_cap, kan::kChainAdjointMaxSteps);
     if (cap < 1) {
@@ -110,22 +121,66 @@ static kanode_status chain_train_wg(kanode_handle* h, int64_t batch, kan::ChainT
         cap = largest(true);
         if (cap < 64) cap = largest(false);
     }
-    if (!a->adaptive && h->opt.fused_solve_cap < 1)
-        cap = std::max<int64_t>(kanode_fixed_step_count(a->t0, a->tf, a->dt, kan::kChainAdjointMaxSteps), 1);
+    if (!adaptive && h->opt.fused_solve_cap < 1)
+        cap = std::max<int64_t>(kanode_fixed_step_count(t0, tf, dt, kan::kChainAdjointMaxSteps), 1);
     int dl = 0, sr = 0;
-    if (cap < 1 || !lds(cap, &dl, &sr))
+    if (cap < 1 || !lds(cap, &dl, &sr)) return false;
+    f.cap = cap;
+    f.dl_lds = dl;
+    f.stage_rec = sr;
+    const size_t rec_bytes =
+        sizeof(double) * kan::chain_train_wg_rec_elems((int64_t)h->n_in * batch, cap, n_save, n_save_test);
+    f.rec_bytes = (rec_bytes + 63) & ~(size_t)63;
+    return true;
+}
+// ens: the replicas of ONE launch (kanode_fit_ensemble_tsit5's group), each with a private block of its own; else
+// the single run of kanode_train_tsit5
+static kanode_status chain_train_wg(kanode_handle* h, const char* what, int64_t batch, kan::ChainTrainArgs* a,
+                                    const kan::EnsembleReplicas* ens, const std::vector<char>& meta, int64_t* res,
+                                    hipStream_t st) {
+    TrainWgFit f{};
+    if (!chain_train_wg_fit(h, batch, a->adaptive != 0, a->t0, a->tf, a->dt, a->n_save, a->n_save_test, f))
         return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (the problem does not fit one workgroup's LDS)");
-    a->cap = cap;
-    a->stage_rec = sr;
-    a->dl_lds = dl;
+    const bool wide = h->opt.chain_wide;
+    a->cap = f.cap;
+    a->stage_rec = f.stage_rec;
+    a->dl_lds = f.dl_lds;
     a->B = batch;
     a->N = h->n_in;
-    const size_t rec_bytes =
-        sizeof(double) * kan::chain_train_wg_rec_elems(a->N * batch, cap, a->n_save, a->n_save_test);
-    return train_launch(h, what, a, nullptr, (rec_bytes + 63) & ~(size_t)63, meta, res, st,
-                        [&](const kan::ChainTrainArgs& a0, const kan::ChainTrainArgs*, int64_t) {
-                            return kan::launch_kd_chain_train_wg(h->hlc, h->n_layers, h->dlc(), h->P, batch, wide, a0, st);
+    return train_launch(h, what, a, ens, f.rec_bytes, meta, res, st,
+                        [&](const kan::ChainTrainArgs& a0, const kan::ChainTrainArgs* dargs, int64_t R) {
+                            return dargs ? kan::launch_kd_chain_train_wg_ensemble(h->hlc, h->n_layers, h->dlc(), h->P,
+                                                                                  batch, wide, a0, dargs, R, st)
+                                         : kan::launch_kd_chain_train_wg(h->hlc, h->n_layers, h->dlc(), h->P, batch,
+                                                                         wide, a0, st);
                         });
+}
+int64_t kanode_internal_fit_ensemble_group(const kanode_handle* h, int64_t batch, bool adaptive, double t0, double tf,
+                                           double dt, int64_t n_save, int64_t n_save_test) {
+    TrainWgFit f{};
+    if (batch < 1 || n_save < 1 || n_save_test < 0 || !(tf > t0) || !kanode_internal_fit_ensemble_ok(h, batch) ||
+        !chain_train_wg_fit(h, batch, adaptive, t0, tf, dt, n_save, n_save_test, f))
+        return 0;
+    return kan::ensemble_group(kan::kTrainMaxReplicas, f.rec_bytes, sizeof(kan::ChainTrainArgs),
+                               kan::ensemble_meta_bound(n_save, n_save_test), kan::kEnsembleBudget);
+}
+kanode_status kanode_internal_chain_fit_ensemble(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
+                                                 const kan::EnsembleReplicas* ens, const std::vector<char>& meta,
+                                                 int64_t* res, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const char* what = "kanode_fit_ensemble_tsit5";
+    if (!ens || !kanode_internal_fit_ensemble_ok(h, batch))
+        return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported");
+    const int64_t G = kanode_internal_fit_ensemble_group(h, batch, a->adaptive != 0, a->t0, a->tf, a->dt, a->n_save,
+                                                         a->n_save_test);
+    if (G < 1)
+        return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (the problem does not fit one workgroup's LDS)");
+    // consecutive groups of G replicas, one launch each on the stream, by the same code path (usually one group)
+    for (int64_t g0 = 0; g0 < ens->R; g0 += G) {
+        const kan::EnsembleReplicas e = kan::ensemble_slice(*ens, g0, G);
+        if (const kanode_status r = chain_train_wg(h, what, batch, a, &e, meta, res + 2 * g0, st); r != KANODE_OK) return r;
+    }
+    return KANODE_OK;
 }
 kanode_status kanode_internal_chain_train(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
                                           const kan::EnsembleReplicas* ens, const std::vector<char>& meta, int64_t* res,
@@ -133,10 +188,11 @@ kanode_status kanode_internal_chain_train(kanode_handle* h, int64_t batch, kan::
     const hipStream_t st = (hipStream_t)stream;
     const char* what = ens ? "kanode_train_ensemble_tsit5" : "kanode_train_tsit5";
     if (!chain_train_lv_ok(h, batch)) {
-        if (ens || !chain_train_wg_ok(h, batch))   // (an ensemble of general chains is out of scope: nothing launched)
+        if (ens || !chain_train_wg_ok(h, batch))   // (an ensemble of general chains is kanode_fit_ensemble_tsit5's)
             return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (the ensemble entry covers one "
-                                                                       "Lotka-Volterra trajectory per replica)");
-        return chain_train_wg(h, batch, a, meta, res, st);
+                                                                       "Lotka-Volterra trajectory per replica; "
+                                                                       "kanode_fit_ensemble_tsit5 covers the other small chains)");
+        return chain_train_wg(h, what, batch, a, nullptr, meta, res, st);
     }
     // the dense-output capacity of one forward solve: KANODE_OPT_FUSED_SOLVE_CAP, else the most steps whose dense
     // output still fits in LDS next to the rest (at least 64: a smaller block stays in global memory instead)

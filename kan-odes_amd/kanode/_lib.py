@@ -187,6 +187,10 @@ SIGNATURES = [
                                              C.POINTER(C.c_int64), C.POINTER(C.c_int32), _P]),
     ("kanode_train_ensemble_tsit5", C.c_int, _ENSEMBLE_ARGS),
     ("kanode_train_forward_ensemble_tsit5", C.c_int, _ENSEMBLE_ARGS),
+    ("kanode_fit_ensemble_supported", C.c_int32, [_H, C.c_int64]),
+    ("kanode_fit_ensemble_group", C.c_int64, [_H, C.c_int64, C.c_double, C.c_double, C.c_int64, C.c_int64,
+                                              C.POINTER(SolverOptsC)]),
+    ("kanode_fit_ensemble_tsit5", C.c_int, _ENSEMBLE_ARGS),
     ("kanode_comm_unique_id", C.c_int, [_P]),
     ("kanode_comm_create", C.c_int, [C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(_P)]),
     ("kanode_comm_allreduce_sum", C.c_int, [_P, _P, C.c_int64, C.c_int32, _P]),

@@ -514,6 +514,28 @@ class KanodeHandle:
         return self._train_ensemble("kanode_train_forward_ensemble_tsit5", p, m, v, u0, t0, tf, saveat, target, opts,
                                     eta, l1, beta, eps, beta_t, n_iters, test, record)
 
+    def fit_ensemble_supported(self, batch: int) -> bool:
+        """kanode_fit_ensemble_supported: fit_ensemble_tsit5 covers this handle at `batch` trajectories: exactly the
+        shapes train_supported gains with `train_any_chain` on (the option is not read), never the Lotka-Volterra
+        shape (train_ensemble_tsit5's)."""
+        return bool(L.lib().kanode_fit_ensemble_supported(self._h, int(batch)))
+
+    def fit_ensemble_group(self, batch: int, t0: float, tf: float, n_save: int, n_save_test: int,
+                           opts: "L.SolverOptsC") -> int:
+        """kanode_fit_ensemble_group: the replicas fit_ensemble_tsit5 puts into one launch for this problem (its
+        256 MiB cap on the handle's buffer; more replicas run in consecutive groups of this size), 0 where the
+        problem is not covered or does not fit one workgroup's LDS."""
+        return int(L.lib().kanode_fit_ensemble_group(self._h, int(batch), float(t0), float(tf), int(n_save),
+                                                     int(n_save_test), C.byref(opts)))
+
+    def fit_ensemble_tsit5(self, p, m, v, u0, t0: float, tf: float, saveat, target, opts: "L.SolverOptsC", eta,
+                           beta, eps: float, beta_t, n_iters: int, test=None, record: bool = False, l1=None):
+        """train_ensemble_tsit5 for every other small fp64 chain (kanode_fit_ensemble_tsit5: a pruned [2,k,2], a
+        [3,6,3] chain, three layers, up to 16 trajectories): the same arguments and the same dict; replica r equals
+        train_tsit5 with `train_any_chain` on, bit for bit.  The Lotka-Volterra shape raises "not supported"."""
+        return self._train_ensemble("kanode_fit_ensemble_tsit5", p, m, v, u0, t0, tf, saveat, target, opts, eta, l1,
+                                    beta, eps, beta_t, n_iters, test, record)
+
     def _train_ensemble(self, name, p, m, v, u0, t0, tf, saveat, target, opts, eta, l1, beta, eps, beta_t, n_iters,
                         test, record):
         B = u0.shape[0] if u0.dim() == 2 else 1

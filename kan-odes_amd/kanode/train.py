@@ -423,7 +423,14 @@ class EnsembleTrainer:
     pairs of running powers), history (R lists), stopped ({r: (iterations the replica had done, reason)})."""
 
     def __init__(self, rhs, u0, tspan, saveat, target, p0, eta=5e-4, solver: Tsit5Options | None = None,
-                 sparse_reg=0.0, sensealg: str | None = None):
+                 sparse_reg=0.0, sensealg: str | None = None, device_loop: str = "default"):
+        """device_loop: Trainer's keyword, for every member.  "default": the device path is one Lotka-Volterra
+        trajectory (and the Fisher-KPP forward loop).  "any": also every other small fp64 chain of
+        Trainer(device_loop="any"), through kanode_fit_ensemble_tsit5; the Lotka-Volterra shape keeps its own entry
+        and its bits."""
+        if device_loop not in ("default", "any"):
+            raise ValueError(f"EnsembleTrainer: device_loop must be 'default' or 'any', not {device_loop!r}")
+        self.device_loop = device_loop
         if not isinstance(p0, torch.Tensor) or p0.dim() != 2 or p0.shape[0] < 1:
             raise ValueError("EnsembleTrainer: p0 must be a tensor of shape [R, P]")
         R = int(p0.shape[0])
@@ -442,7 +449,7 @@ class EnsembleTrainer:
         self._members = []
         for r in range(R):        # replica r's Trainer works on row r of p, m, v in place
             tr = Trainer(rhs, u0, tspan, saveat, target, self.p[r], eta=self.eta[r], solver=self.solver,
-                         sparse_reg=self.sparse_reg[r], sensealg=sensealg)
+                         sparse_reg=self.sparse_reg[r], sensealg=sensealg, device_loop=device_loop)
             tr.p = self.p[r]
             tr.opt.state[id(tr.p)] = [self.m[r], self.v[r], list(tr.opt.beta)]
             self._members.append(tr)
@@ -467,7 +474,8 @@ class EnsembleTrainer:
         prune it or checkpoint it.  The ensemble is not changed by what happens to it."""
         src = self._members[r]
         tr = Trainer(self.rhs, self.u0, self.tspan, self.saveat, self.target, self.p[r], eta=self.eta[r],
-                     solver=self.solver, sparse_reg=self.sparse_reg[r], sensealg=src.sensealg)
+                     solver=self.solver, sparse_reg=self.sparse_reg[r], sensealg=src.sensealg,
+                     device_loop=self.device_loop)
         tr.opt.state[id(tr.p)] = [self.m[r].clone(), self.v[r].clone(), list(self.bp[r])]
         tr.history = list(src.history)
         tr._pver = src._pver
@@ -509,8 +517,10 @@ class EnsembleTrainer:
     def _device_path(self, with_test: bool):
         probe = next((tr for tr in self._members if tr.sparse_reg), self._members[0])
         hd = getattr(self.rhs, "hd", None)
+        if self.device_loop == "any":                     # (the members turn the option on, as Trainer.run does)
+            return probe._native_run_path(with_test)
         if hd is not None and self.p.is_cuda and hd.get_option("train_any_chain"):
-            with hd.options(train_any_chain=0):           # (the ensemble entry is the Lotka-Volterra shape's alone)
+            with hd.options(train_any_chain=0):           # (the default's ensemble entry is the Lotka-Volterra shape's)
                 return probe._native_run_path(with_test)
         return probe._native_run_path(with_test)          # (a penalty on any replica sends a Fisher-KPP field to the host)
 
@@ -591,6 +601,9 @@ class EnsembleTrainer:
         oc = self.solver.to_c()
         target = self.target.contiguous()
         call = hd.train_forward_ensemble_tsit5 if forward else hd.train_ensemble_tsit5
+        B = self.u0.shape[0] if self.u0.dim() == 2 else 1
+        if not forward and self.device_loop == "any" and hd.fit_ensemble_supported(B):
+            call = hd.fit_ensemble_tsit5                      # (every small chain but the Lotka-Volterra shape)
         bps = self.bp
         keys = ("loss", "loss_test") + (("grad", "p_before", "counts") if record else ())
         at = 0
