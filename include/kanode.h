@@ -668,6 +668,38 @@ kanode_status kanode_solve_ensemble_tsit5(kanode_handle* h, int64_t n_replicas, 
                                           void* u_save, const kanode_solver_options* opt, kanode_solve_stats* stats,
                                           int32_t* stop, void* stream);
 
+/* --- trajectory ensemble: n_traj initial conditions, each its own ODE, in ONE launch -----------
+ * kanode_solve_tsit5 with a batch solves ONE ODE over all N*B entries: one error norm, one step size, and the hardest
+ * trajectory sets the step count of all.  This entry is the other reading of "many initial conditions" (SciML's
+ * EnsembleProblem over u0): trajectory r is solved as kanode_solve_tsit5 solves u0 + r*N at batch 1 (control = auto,
+ * no dense output), with its own error norm, step sizes, rejections and counters, bit for bit, and no trajectory
+ * reads another's data or waits for it.  A 16-lane row of a wave carries a trajectory, a launch n_traj / 4 waves.
+ *
+ *     p             device [P], shared by all trajectories, as are t0, tf, saveat and the options
+ *     u0            device [n_traj][N], contiguous
+ *     saveat        host, ascending within [t0, tf]; n_save >= 1
+ *     u_save        device [n_save][n_traj][N]: the layout kanode_solve_tsit5 gives a batch of n_traj
+ *     opt           as kanode_solve_tsit5's, checked by the same statements; control is not read
+ *     stats, stop   host arrays [n_traj]: the counters, and a kanode_solve_stop
+ * 1 <= n_traj <= 65536.  The status words and the device copy of saveat live on the handle and are reused
+ * (kanode_reserve does not cover them: the call may allocate).  Every other path of the handle is left as it was.
+ *
+ * A trajectory that reaches maxiters stops alone: stop[r] = KANODE_SOLVE_MAXITERS, stats[r] holds its counters, and
+ * its entries of the u_save rows past the last saveat value it reached are LEFT AS THE CALLER PASSED THEM.  The call
+ * synchronises the stream (it reads the status words) and returns KANODE_OK whenever the launch ran;
+ * kanode_last_error then names the lowest stopped trajectory.
+ *
+ * Covered (kanode_solve_trajectories_supported): chain handles for which kanode_solve_tsit5 with control = auto runs
+ * as one workgroup at batch 1: layers at most 16 wide, n_in == n_out, fp64 and fp32, KANODE_OPT_FUSED_SOLVE on.  Not
+ * the Fisher-KPP field (a wave per field is what kanode_solve_ensemble_tsit5 is) and not wider chains:
+ * KANODE_ERR_UNSUPPORTED, nothing launched and nothing written.  A capturing stream is refused
+ * (KANODE_ERR_CAPTURE). */
+int32_t kanode_solve_trajectories_supported(const kanode_handle* h);
+kanode_status kanode_solve_trajectories_tsit5(kanode_handle* h, const void* p, const void* u0, int64_t n_traj,
+                                              double t0, double tf, const double* saveat, int64_t n_save,
+                                              void* u_save, const kanode_solver_options* opt,
+                                              kanode_solve_stats* stats, int32_t* stop, void* stream);
+
 /* --- the data-parallel gradient all-reduce (one process per GPU) -----------------
  * For hosts without a collective of their own (Julia, C): after kanode_adjoint_tsit5 on each rank's
  * trajectory shard, the flat [dp; L] is SUM all-reduced in place over RCCL (xGMI inside a node), then

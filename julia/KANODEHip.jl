@@ -640,6 +640,45 @@ function solve_ensemble_tsit5(h::Handle, u0::AbstractVecOrMat, tspan, ps::Abstra
     return sol, stats, stop
 end
 
+# --- the trajectory ensemble (kanode_solve_trajectories_tsit5): the forward solves of one problem at one p from R
+# initial conditions in one launch, every trajectory an ODE of its own (EnsembleProblem over u0): a trained network
+# on held-out initial conditions, a phase portrait, generated data.
+solve_trajectories_supported(h::Handle) =
+    ccall(sym(:kanode_solve_trajectories_supported), Int32, (Ptr{Cvoid},), h.ptr) == 1
+
+"""solve_trajectories(h, u0, tspan, p, saveat; abstol, reltol, dt, adaptive, ...) -> (sol, stats, stop).
+u0 is [N, R]: column r holds trajectory r's initial condition (the C side's [R][N]).  Every trajectory is solved on its
+own, with its own error norm, step sizes and rejections, as solve_tsit5 solves u0[:, r] alone, bit for bit, where
+solve_tsit5 with the matrix u0 solves ONE ODE over all N*R entries.  sol is [N, R, n_save], the layout solve_tsit5 gives
+that matrix, filled with NaN beforehand; stats a vector of R SolveStats; stop[r] is 0, or 1 where trajectory r reached
+maxiters (a kanode_solve_stop: it does not throw, and its columns past the last stop it reached stay NaN).  Up to 65536
+trajectories per call.  Covered: solve_trajectories_supported(h), i.e. chains where solve_tsit5 runs as one workgroup
+at one trajectory."""
+function solve_trajectories(h::Handle, u0::AbstractMatrix, tspan, p::AbstractVector, saveat::AbstractVector; kw...)
+    checkp(h, p)
+    checku(h, u0, h.nin, "u0")
+    h.nin == h.nout || throw(ArgumentError("an ODE RHS needs a chain with in_dims == out_dims"))
+    T = h.T
+    R = size(u0, 2)
+    1 <= R <= 65536 || throw(ArgumentError("solve_trajectories: 1 <= R <= 65536 trajectories"))
+    ts = Vector{Float64}(saveat)
+    (issorted(ts) && !isempty(ts)) || throw(ArgumentError("saveat must be ascending and not empty"))
+    solve_trajectories_supported(h) || throw(ArgumentError("solve_trajectories: not covered for this handle"))
+    opt = options(; kw...)
+    pd, ud = upload(tohost(T, p)), upload(tohost(T, u0))
+    out = fill(T(NaN), h.nin, R, length(ts))
+    od = upload(out)
+    stats = Vector{SolveStats}(undef, R)
+    stop = zeros(Int32, R)
+    st = GC.@preserve ts stats stop ccall(sym(:kanode_solve_trajectories_tsit5), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float64}, Int64, Ptr{Cvoid},
+         Ref{SolverOptions}, Ptr{SolveStats}, Ptr{Int32}, Ptr{Cvoid}),
+        h.ptr, pd.ptr, ud.ptr, R, tspan[1], tspan[2], ts, length(ts), od.ptr, opt, stats, stop, C_NULL)
+    check(h, st)
+    download!(out, od)
+    return out, stats, stop
+end
+
 # --- pruning a sparsified KAN (LV_driver_KANODE.jl:52-108): per-edge scores on the device, the keep rule and the
 # parameter slicing on the host.  Scores are Julia [O, I] matrices (the memory kanode_edge_scores writes).
 layer_length(h::Handle, i::Integer) = Int(ccall(sym(:kanode_layer_param_length), Int64, (Ptr{Cvoid}, Int32), h.ptr, i))

@@ -135,4 +135,33 @@ inline size_t ens_solve_save_elem(int64_t r, int64_t n_save, int64_t n) {
     return (size_t)r * (size_t)n_save * (size_t)n;
 }
 
+// ---- the trajectory solve (kanode_solve_trajectories_tsit5, kan_traj_solve.hip) ----------------------------------
+// R forward solves of one problem at one p from R initial conditions, each with its own step control, a 16-lane row
+// per trajectory.  The handle's buffer of a call (its own, laid out as the ensemble solve's):
+//     status [R][4] int64 (naccept, nreject, nf, stop) | saveat [n_save] doubles | 64 spare bytes
+// The caller's arrays are dense and trajectory-minor, the layout a batched solve of R trajectories has: u0 [R][N],
+// u_save [n_save][R][N].
+constexpr int kTrajSolveStatusWords = 4;
+constexpr int kTrajPerWave = 4;   // 16-lane rows of a 64-lane wave
+struct TrajSolveLayout {
+    size_t off_saveat, bytes;
+};
+inline TrajSolveLayout traj_solve_layout(int64_t R, int64_t n_save) {
+    TrajSolveLayout L;
+    L.off_saveat = ensemble_round((size_t)R * kTrajSolveStatusWords * sizeof(int64_t));
+    L.bytes = ensemble_round(L.off_saveat + (size_t)n_save * sizeof(double)) + 64;
+    return L;
+}
+// the host copy of the status words
+inline size_t traj_solve_status_bytes(int64_t R) { return (size_t)R * kTrajSolveStatusWords * sizeof(int64_t); }
+// trajectory r's status words, in int64 words from the buffer's start
+inline size_t traj_solve_status_word(int64_t r) { return (size_t)r * kTrajSolveStatusWords; }
+// entry j of trajectory r in u0, and in row si of u_save, in elements from the array's start
+inline size_t traj_solve_u0_elem(int64_t r, int64_t N, int64_t j) { return (size_t)r * (size_t)N + (size_t)j; }
+inline size_t traj_solve_save_elem(int64_t si, int64_t r, int64_t R, int64_t N, int64_t j) {
+    return ((size_t)si * (size_t)R + (size_t)r) * (size_t)N + (size_t)j;
+}
+// one-wave workgroups of a launch of R trajectories
+inline int64_t traj_solve_waves(int64_t R) { return (R + kTrajPerWave - 1) / kTrajPerWave; }
+
 }  // namespace kan

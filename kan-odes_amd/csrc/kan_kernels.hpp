@@ -652,6 +652,16 @@ hipError_t launch_fk_small_tsit5_ens(const LayerConst& hlc, const PPConst& hpc, 
                                      const PPConst* pc, const double* p, int64_t P, double* tables,
                                      int64_t table_stride, const FkSmallArgs& s, const double* u0, int64_t B,
                                      const ChainSolveArgs& a, int64_t n_rep, hipStream_t st);
+// The trajectory solve (kan_traj_solve.hip): R (<= kTrajMaxTrajectories) solves of one small chain at one p from the
+// rows of u0 [R][N], each an ODE of its own (its own error norm, step sizes and counters), a 16-lane row per
+// trajectory and four trajectories per one-wave workgroup; u_save [n_save][R][N], out + 4r the counters of
+// trajectory r; saveat and the options shared, no dense output (a.rec null, a.cap 0).  Covers what
+// launch_kd_chain_tsit5 covers at B = 1.
+constexpr int64_t kTrajMaxTrajectories = 65536;
+bool chain_tsit5_traj_supported(const LayerConst* hlcs, int nl, int64_t P, size_t esize);
+template <typename T>
+hipError_t launch_kd_chain_tsit5_traj(const LayerConst* hlcs, int nl, const LayerConst* lcs, const T* p, int64_t P,
+                                      const T* u0, int64_t R, const ChainSolveArgs& a, hipStream_t st);
 
 // surrogate shapes (kan_wide.hip)
 constexpr int kWideKT = 8;       // column tile of the wide-out kernels

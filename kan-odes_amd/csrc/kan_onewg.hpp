@@ -46,22 +46,44 @@ __device__ __forceinline__ double onewg_bsum(double v, double* red) {
     for (int w = 1; w < (int)(blockDim.x / kWave); ++w) t += red[w];
     return t;
 }
+// Σ over the calling 16-lane row of v, the same total in every lane of the row: wave_sum's butterfly restricted to
+// the row (lane offsets 8, 4, 2, 1).  Where a problem holds one row of a one-wave block, wave_sum's offsets 32 and
+// 16 add the other rows' zeros to a sum of squares, which changes no bit, so this is onewg_bsum's total of that
+// block bit for bit.  (row16_sum pairs other lanes: another order, other bits from three entries on.)  Every source
+// lane is in the caller's row, so rows of a wave may call it under different control flow.
+__device__ __forceinline__ double onewg_rsum(double v) {
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+    return v;
+}
 
 // The forward solve (solve_t): u0[n] -> u_save [n_save][n], the dense output and the counters in a.out.
 // WAVE: the whole problem lives on the calling wave (other waves of the block may do something else meanwhile):
 // the error norm is the wave sum alone (what onewg_bsum returns in a one-wave block, bit for bit: the other
 // waves' zeros change no bit of a sum of squares), no block barrier is executed, red is unused and the wave's
 // lane 0 writes the step records and counters.  a's pointers may then be LDS addresses.
-template <typename T, class Mdl, bool WAVE = false>
+// ROW: the whole problem lives on the calling 16-lane row, and the four rows of a wave solve four problems that
+// share nothing but the instruction stream (kan_traj_solve.hip): each row takes its own step-control decisions, so
+// the rows of a wave reject, save and finish on their own.  The error norm is the row sum (onewg_rsum: the bits of
+// the wave sum of a one-row problem) over m.nrow entries, where m.n is only the stride between two saveat rows;
+// the row's lane 0 writes the counters; no barrier of any kind is executed and red is unused.  The model's rhs must
+// be local to the row.  a.out is then this row's own (the caller offsets it); there is no dense output.
+template <typename T, class Mdl, bool WAVE = false, bool ROW = false>
 __device__ __forceinline__ void onewg_tsit5(Mdl& m, const T* __restrict__ u0, const ChainSolveArgs& a, double* red) {
     using K = Tsit5Tab;
+    static_assert(!(WAVE && ROW), "one of the two sub-block modes");
     const bool act = m.act;
     const int64_t idx = m.idx, n = m.n;
+    auto nn = [&]() -> double {   // the entries of the error norm
+        if constexpr (ROW) return (double)m.nrow;
+        else return (double)n;
+    };
     T* __restrict__ usave = reinterpret_cast<T*>(a.u_save);
     T* __restrict__ rec = reinterpret_cast<T*>(a.rec);
-    const bool lead = WAVE ? (threadIdx.x & (kWave - 1)) == 0 : threadIdx.x == 0;
+    const bool lead = ROW ? (threadIdx.x & 15) == 0 : WAVE ? (threadIdx.x & (kWave - 1)) == 0 : threadIdx.x == 0;
     auto bsum = [&](double v) -> double {
-        if constexpr (WAVE) return wave_sum(act ? v : 0.0);
+        if constexpr (ROW) return onewg_rsum(act ? v : 0.0);
+        else if constexpr (WAVE) return wave_sum(act ? v : 0.0);
         else return onewg_bsum(act ? v : 0.0, red);
     };
     T u = act ? u0[idx] : T(0);
@@ -77,13 +99,13 @@ __device__ __forceinline__ void onewg_tsit5(Mdl& m, const T* __restrict__ u0, co
     double dt = a.dt;
     if (a.adaptive && !(a.dt > 0)) {   // Hairer & Wanner (solve_t initdt)
         const double sk = ::fma(a.reltol, kabs((double)u), a.abstol);
-        const double d0 = ::sqrt(bsum(((double)u / sk) * ((double)u / sk)) / (double)n);
-        const double d1 = ::sqrt(bsum(((double)k[0] / sk) * ((double)k[0] / sk)) / (double)n);
+        const double d0 = ::sqrt(bsum(((double)u / sk) * ((double)u / sk)) / nn());
+        const double d1 = ::sqrt(bsum(((double)k[0] / sk) * ((double)k[0] / sk)) / nn());
         double dt0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
         dt0 = ::fmin(dt0, tf - t0);
         const T f1 = m.rhs(kfma<T>((T)dt0, k[0], u));
         const double e = ::fma(-1.0, (double)k[0], (double)f1) / sk;
-        const double d2 = ::sqrt(bsum(e * e) / (double)n) / dt0;
+        const double d2 = ::sqrt(bsum(e * e) / nn()) / dt0;
         const double mx = ::fmax(d1, d2);
         const double dt1 = mx <= 1e-15 ? ::fmax(1e-6, dt0 * 1e-3) : ::pow(0.01 / mx, 1.0 / 5.0);
         dt = ::fmin(::fmin(100 * dt0, dt1), tf - t0);
@@ -110,7 +132,7 @@ __device__ __forceinline__ void onewg_tsit5(Mdl& m, const T* __restrict__ u0, co
             const double e = ::fma(dt * K::BT[6], (double)k[6], ev);
             const double sk = ::fma(a.reltol, ::fmax(kabs((double)u), kabs((double)y)), a.abstol);
             const double r = e / sk;
-            const double eest = ::sqrt(bsum(r * r) / (double)n);
+            const double eest = ::sqrt(bsum(r * r) / nn());
             const double q11 = eest > 0 ? KAN_ONEWG_POW(eest, a.beta1) : 0.0;
             if (eest > 1.0 && dt > a.dtmin) {
                 ++nreject;

@@ -354,6 +354,42 @@ kanode_status kanode_internal_solve_ens(kanode_handle* h, const void* p, int64_t
     std::memcpy(res, h->ens_solve_host.ptr(), res_bytes);
     return KANODE_OK;
 }
+// the trajectory solve: a chain that kanode_internal_chain_tsit5 launches for at batch 1 (the Fisher-KPP field spends
+// a wave per field, which the ensemble solve already is)
+bool kanode_internal_solve_traj_ok(const kanode_handle* h) {
+    if (h->spec.rhs_kind != KANODE_RHS_CHAIN || fk_small_ok(h, 1)) return false;
+    if (!kanode_internal_chain_tsit5_ok(h, 1) || h->n_in != h->n_out) return false;
+    return kan::chain_tsit5_traj_supported(h->hlc, h->n_layers, h->P, h->esize);
+}
+kanode_status kanode_internal_solve_traj(kanode_handle* h, const void* p, const void* u0, int64_t R,
+                                         kan::ChainSolveArgs* a, const double* saveat, int64_t n_save, int64_t* res,
+                                         void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const char* what = "kanode_solve_trajectories_tsit5";
+    const kan::TrajSolveLayout L = kan::traj_solve_layout(R, n_save);
+    const size_t res_bytes = kan::traj_solve_status_bytes(R);
+    if (h->traj_solve_buf.bytes() < L.bytes || h->traj_solve_host.bytes() < res_bytes) {
+        HIP_TRY(h, hipStreamSynchronize(st));   // (an earlier call's kernels may still use the old buffers)
+        if (h->traj_solve_buf.reserve(L.bytes) != hipSuccess || h->traj_solve_host.reserve(res_bytes) != hipSuccess)
+            return fail(h, KANODE_ERR_ALLOC, std::string(what) + ": out of memory for the trajectories' status words");
+    }
+    char* const base = h->traj_solve_buf.as<char>();
+    // (the call synchronises before it returns, so the caller's list outlives the copy)
+    HIP_TRY(h, hipMemcpyAsync(base + L.off_saveat, saveat, (size_t)n_save * sizeof(double), hipMemcpyHostToDevice, st));
+    a->saveat = reinterpret_cast<const double*>(base + L.off_saveat);
+    a->out = reinterpret_cast<int64_t*>(base);
+    const hipError_t e = by_dtype(h, [&](auto t) {
+        using T = decltype(t);
+        return kan::launch_kd_chain_tsit5_traj<T>(h->hlc, h->n_layers, h->dlc(), (const T*)p, h->P, (const T*)u0, R, *a,
+                                                  st);
+    });
+    if (e == hipErrorNotSupported) return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported");
+    if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(h->traj_solve_host.ptr(), base, res_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    std::memcpy(res, h->traj_solve_host.ptr(), res_bytes);
+    return KANODE_OK;
+}
 
 // ---- the persistent surrogate-pair adjoint ----
 bool kanode_internal_pair_persist_ok(const kanode_handle* h) {

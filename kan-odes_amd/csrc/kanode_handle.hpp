@@ -70,6 +70,10 @@ struct kanode_handle {
     // the single-replica paths left them).  Grow-only; kanode_reserve does not cover them.
     kan::DevBuf ens_solve_buf, ens_tables;
     kan::PinnedBuf ens_solve_host;
+    // the trajectory solve (kanode_solve_trajectories_tsit5; kan_ensemble.hpp): status words | saveat, and the host
+    // copy of the status words.  Grow-only; kanode_reserve does not cover them.
+    kan::DevBuf traj_solve_buf;
+    kan::PinnedBuf traj_solve_host;
     // table reuse inside one integrator solve (p constant): build each table set once
     bool hold_tables = false;
     bool built_phi = false, built_vjp = false;

@@ -160,6 +160,14 @@ bool kanode_internal_solve_ens_ok(const kanode_handle* h, int64_t batch);
 kanode_status kanode_internal_solve_ens(kanode_handle* h, const void* p, int64_t R, const void* u0, int64_t batch,
                                         kan::ChainSolveArgs* a, const double* saveat, int64_t n_save, int64_t* res,
                                         void* stream);
+// the trajectory solve (kanode_solve_trajectories_tsit5; kan_traj_solve.hip): whether the handle takes it (a chain
+// where kanode_internal_chain_tsit5 launches at batch 1; not the Fisher-KPP field), and the call: R trajectories
+// from u0 [R][N] at one p, a's saveat and out set here (the handle's buffer; saveat is the host list).  Synchronises;
+// res = [R][4]: naccept, nreject, nf, status.
+bool kanode_internal_solve_traj_ok(const kanode_handle* h);
+kanode_status kanode_internal_solve_traj(kanode_handle* h, const void* p, const void* u0, int64_t R,
+                                         kan::ChainSolveArgs* a, const double* saveat, int64_t n_save, int64_t* res,
+                                         void* stream);
 // the persistent surrogate-pair adjoint (kd_pair_adjoint_kernel): whether the handle takes it
 // (KANODE_OPT_PAIR_PERSIST, fp64 surrogate pair), its workgroup count, and the launch (launched =
 // false when the kernel does not cover the shape / batch)

@@ -361,6 +361,37 @@ class KanodeHandle:
         stats = [dict(naccept=st[r].naccept, nreject=st[r].nreject, nf=st[r].nf) for r in range(R)]
         return u_save, stats, [L.SOLVE_STOP.get(int(stop[r]), str(stop[r])) for r in range(R)]
 
+    def solve_trajectories_supported(self) -> bool:
+        """kanode_solve_trajectories_supported: the trajectory solve covers this handle (a chain where solve_tsit5
+        with control = auto runs as one workgroup at batch 1)."""
+        return bool(L.lib().kanode_solve_trajectories_supported(self._h))
+
+    def solve_trajectories_tsit5(self, p: torch.Tensor, u0: torch.Tensor, t0: float, tf: float, saveat,
+                                 opts: "L.SolverOptsC"):
+        """The solve of solve_tsit5 from every row of u0 [R, N] on its own, in one launch, a 16-lane row per
+        trajectory (kanode_solve_trajectories_tsit5): every trajectory has its own error norm, step sizes and
+        counters, where solve_tsit5 at u0 solves ONE ODE over all R·N entries.  Returns (u_save (len(saveat), R, N),
+        stats (R dicts), stop (R names of _lib.SOLVE_STOP)).  u_save is pre-filled with NaN: a trajectory that
+        reached maxiters ("maxiters", no exception) leaves its entries of the rows past its last reached stop that
+        way.  An unsupported handle or a bad argument raises KanodeError."""
+        self._check_t(p, (self.P,), "p")
+        if u0.dim() != 2:
+            raise ValueError("solve_trajectories_tsit5 needs u0 of shape [R, N]")
+        R = int(u0.shape[0])
+        self._check_t(u0, (R, self.N), "u0")
+        if self.N_out != self.N:
+            raise ValueError("solve needs an RHS with N_in == N_out")
+        sv = self._saveat_c(saveat)
+        u_save = torch.full((len(saveat), R, self.N), float("nan"), dtype=self.dtype, device=self.device)
+        st = (L.SolveStatsC * max(R, 1))()
+        stop = (C.c_int32 * max(R, 1))()
+        L.check(L.lib().kanode_solve_trajectories_tsit5(self._h, _ptr(p), _ptr(u0), R, float(t0), float(tf), sv,
+                                                        len(saveat), _ptr(u_save), C.byref(opts), st, stop,
+                                                        _stream(self.device)), self._h,
+                "kanode_solve_trajectories_tsit5")
+        stats = [dict(naccept=st[r].naccept, nreject=st[r].nreject, nf=st[r].nf) for r in range(R)]
+        return u_save, stats, [L.SOLVE_STOP.get(int(stop[r]), str(stop[r])) for r in range(R)]
+
     def _saveat_c(self, saveat):
         key = tuple(saveat)
         cache = self.__dict__.setdefault("_saveat_cache", {})

@@ -389,3 +389,75 @@ def solve_ensemble(f, u0: torch.Tensor, tspan, ps: torch.Tensor, saveat=None,
             stats.append(sol.stats)
             stop.append("ok")
         return EnsembleSolution(list(saveat), u, stats, stop, "host")
+
+
+@dataclass
+class TrajectorySolution:
+    """solve_trajectories' result: t (the saveat list), u (len(t), R, N), stats (R dicts), stop (R of "ok" /
+    "maxiters"; a stopped trajectory's column u[:, r] is all NaN) and the path taken ("device": one launch per 65536
+    trajectories, "host": a loop of solve() at batch 1)."""
+    t: list
+    u: torch.Tensor
+    stats: list
+    stop: list
+    path: str
+
+
+TRAJECTORIES_MAX = 65536   # trajectories of one kanode_solve_trajectories_tsit5 call (kTrajMaxTrajectories)
+
+
+def solve_trajectories(f, u0: torch.Tensor, tspan, p: torch.Tensor, saveat=None,
+                       opt: Tsit5Options | None = None) -> TrajectorySolution:
+    """solve(f, u0[r:r+1], tspan, p, saveat, opt) for every row of u0 [R, N], without gradients (the inputs are
+    detached): an ensemble over initial conditions (SciML's EnsembleProblem over u0), every trajectory an ODE of its
+    own with its own error norm, step sizes and rejections -- a trained network on held-out initial conditions, a
+    phase portrait, generated data.  (solve(f, u0, ...) with the matrix u0 is the other reading: ONE ODE over all R·N
+    entries, one step size for all, and u has that call's layout, so one call swaps for the other.)
+
+    Where solve() would run in libkanode and the handle covers the shape (KanodeHandle.solve_trajectories_supported:
+    the one-workgroup chain solves) all trajectories go through ONE launch per 65536, a 16-lane row each, and column
+    r has the bits of solve() at u0[r:r+1].  Otherwise the host path: a loop of solve().  A trajectory whose solve
+    reaches maxiters does not raise on either path: stop[r] is "maxiters" and u[:, r] is all NaN."""
+    from . import _lib as L
+    opt = opt or Tsit5Options()
+    if not isinstance(u0, torch.Tensor) or u0.dim() != 2 or u0.shape[0] < 1:
+        raise ValueError("solve_trajectories: u0 must be a tensor of shape [R, N]")
+    t0, tf = float(tspan[0]), float(tspan[1])
+    saveat = _saveat_list(tspan, saveat)
+    u0 = u0.detach()
+    p = p.detach() if isinstance(p, torch.Tensor) else p
+    R, N = int(u0.shape[0]), int(u0.shape[1])
+    native = native_ok(f, u0, tspan, p, saveat, opt)
+    if native:
+        tol = 1e-12 * max(1.0, abs(tf))
+        saveat = [s for s in saveat if s <= tf + tol]
+    nan = float("nan")
+    with torch.no_grad():
+        if native and len(saveat) >= 1 and f.hd.solve_trajectories_supported():
+            pc, u0c, oc = p.contiguous(), u0.contiguous(), opt.to_c()
+            us, stats, stop = [], [], []
+            for a in range(0, R, TRAJECTORIES_MAX):
+                u, st, sp = f.hd.solve_trajectories_tsit5(pc, u0c[a:a + TRAJECTORIES_MAX], t0, tf, saveat, oc)
+                us.append(u)
+                stats += st
+                stop += sp
+            u = us[0] if len(us) == 1 else torch.cat(us, dim=1)
+            for r, s in enumerate(stop):
+                if s != "ok":
+                    u[:, r] = nan
+            return TrajectorySolution(list(saveat), u, stats, stop, "device")
+        u = torch.full((len(saveat), R, N), nan, dtype=u0.dtype, device=u0.device)
+        stats, stop = [], []
+        for r in range(R):
+            try:
+                sol = solve(f, u0[r:r + 1], tspan, p, saveat, opt)
+            except (RuntimeError, L.KanodeError) as e:   # (the Python loop's error, the native one)
+                if "maxiters" not in str(e):
+                    raise
+                stats.append({})
+                stop.append("maxiters")
+                continue
+            u[:sol.u.shape[0], r:r + 1] = sol.u
+            stats.append(sol.stats)
+            stop.append("ok")
+        return TrajectorySolution(list(saveat), u, stats, stop, "host")
