@@ -700,6 +700,60 @@ kanode_status kanode_solve_trajectories_tsit5(kanode_handle* h, const void* p, c
                                               void* u_save, const kanode_solver_options* opt,
                                               kanode_solve_stats* stats, int32_t* stop, void* stream);
 
+/* --- the gradient of a trajectory ensemble: n_traj solves and adjoints of one problem in one launch ----------------
+ * kanode_solve_trajectories_tsit5's reading of "many initial conditions", with the loss and its gradient: trajectory r
+ * is solved from u0 + r*N with its own error norm, step sizes and rejections, its dense output kept, its loss
+ * mse_r = mean((u_r - target[:, r, :])^2) and the cotangent formed, and its InterpolatingAdjoint run with its own step
+ * control, all by one one-wave workgroup (kd_chain_traj_grad_kernel: the phases of kanode_train_tsit5's general loop,
+ * once, at batch 1).  The adjoint always runs on the column-group model, whatever KANODE_OPT_CHAIN_WIDE says:
+ * row r is bit for bit the gradient kanode_solve_tsit5 + kanode_adjoint_tsit5 give at batch 1 on a handle with
+ * KANODE_OPT_CHAIN_WIDE = 0.  Then
+ *     *loss = (sum_r mse_r) / n_traj      (= mean((u - target)^2) over the whole [n_save][n_traj][N] tensor)
+ *     dp[q] = (sum_r dp_rows[r][q]) / n_traj
+ * both summed in an order that depends on n_traj alone: chunks of 64 consecutive trajectories in ascending r from 0.0
+ * with rounded adds, the chunk sums in ascending chunk order from 0.0, one rounded division.  No atomics.
+ *
+ *     p                    device [P], shared by all trajectories, as are t0, tf, saveat and the options
+ *     u0                   device [n_traj][N], contiguous
+ *     saveat               host, ascending within [t0, tf]; n_save >= 1
+ *     target               device [n_save][n_traj][N]
+ *     opt                  as kanode_solve_tsit5's, checked by the same statements; control is not read
+ *     loss                 host: the total
+ *     dp                   device [P]
+ *     dp_rows, loss_rows   device [n_traj][P], [n_traj], or NULL: the per-trajectory gradients and losses
+ *     du0                  device [n_traj][N] or NULL: d mse_r / d u0_r (NOT divided by n_traj)
+ *     u_save               device [n_save][n_traj][N] or NULL; the entries of a trajectory whose FORWARD stopped are
+ *                          left as the caller passed them
+ *     fwd_stats, adj_stats host [n_traj]: the forward's and the adjoint's counters (the adjoint's zero where it did
+ *                          not run)
+ *     stop                 host [n_traj]: a kanode_train_stop (OK, FORWARD_MAXITERS, DENSE_CAPACITY, ADJOINT_MAXITERS,
+ *                          LOSS_NOT_FINITE)
+ * 1 <= n_traj <= 65536.  A trajectory that stops stops alone: its dp_rows / loss_rows / du0 entries are NaN, and so
+ * are *loss and dp (the totals say so without a branch).  The dense-output capacity of a trajectory is decided as
+ * kanode_fit_ensemble_tsit5 decides it (KANODE_OPT_FUSED_SOLVE_CAP, else what fits in LDS, at most 1024 steps; a
+ * fixed-step solve's own count).  Every trajectory has a private dense-output block in a buffer of the handle that is
+ * capped at 256 MiB: the call runs n_traj trajectories as consecutive launch groups of
+ * kanode_trajectories_gradient_group(...) (a multiple of 64, at most 65536; 0 where the problem is not covered), each
+ * one launch on the stream, and the result does not depend on the grouping.  The call makes one device-to-host copy
+ * (the status words and the loss), synchronises once, and returns KANODE_OK whenever the launches ran;
+ * kanode_last_error then names the lowest stopped trajectory.  It adds no handle option and does NOT read the handle's
+ * L1 penalty (kanode_set_l1_penalty is kanode_train_tsit5's; add the term on the host).  kanode_reserve does not cover
+ * the buffer: the call may allocate.  Every other path of the handle is left as it was.
+ *
+ * Covered (kanode_trajectories_gradient_supported): fp64 chain handles that kanode_fit_ensemble_tsit5's kernel covers
+ * at batch 1 with the column-group adjoint: layers at most 16 wide, n_in == n_out, KANODE_OPT_FUSED_SOLVE on; the
+ * unpruned [2,10,2] chain included.  Not fp32, not the Fisher-KPP field, not wider chains: KANODE_ERR_UNSUPPORTED,
+ * nothing launched and nothing written.  A capturing stream is refused (KANODE_ERR_CAPTURE). */
+int32_t kanode_trajectories_gradient_supported(const kanode_handle* h);
+int64_t kanode_trajectories_gradient_group(const kanode_handle* h, double t0, double tf, int64_t n_save,
+                                           const kanode_solver_options* opt);
+kanode_status kanode_trajectories_gradient_tsit5(kanode_handle* h, const void* p, const void* u0, int64_t n_traj,
+                                                 double t0, double tf, const double* saveat, int64_t n_save,
+                                                 const void* target, const kanode_solver_options* opt, double* loss,
+                                                 void* dp, void* dp_rows, void* loss_rows, void* du0, void* u_save,
+                                                 kanode_solve_stats* fwd_stats, kanode_solve_stats* adj_stats,
+                                                 int32_t* stop, void* stream);
+
 /* --- the data-parallel gradient all-reduce (one process per GPU) -----------------
  * For hosts without a collective of their own (Julia, C): after kanode_adjoint_tsit5 on each rank's
  * trajectory shard, the flat [dp; L] is SUM all-reduced in place over RCCL (xGMI inside a node), then

@@ -679,6 +679,55 @@ function solve_trajectories(h::Handle, u0::AbstractMatrix, tspan, p::AbstractVec
     return out, stats, stop
 end
 
+# --- the gradient of a trajectory ensemble (kanode_trajectories_gradient_tsit5): the loss mean((u - target)^2) over R
+# trajectories of one problem at one p and its gradient, every trajectory an ODE of its own with its own forward and
+# adjoint step control, one workgroup each; multi-trajectory training with one controller per trajectory.
+trajectories_gradient_supported(h::Handle) =
+    ccall(sym(:kanode_trajectories_gradient_supported), Int32, (Ptr{Cvoid},), h.ptr) == 1
+
+"""trajectories_gradient(h, u0, tspan, p, saveat, target; abstol, reltol, dt, adaptive, ...) ->
+(loss, dp, dp_rows, loss_rows, fwd_stats, adj_stats, stop).
+u0 is [N, R] (column r: trajectory r's initial condition), target [N, R, n_save], the layout solve_trajectories
+returns.  loss is the mean over the whole tensor, dp [P] its gradient: the mean of the R batch-1 gradients dp_rows
+[P, R], both summed in an order that depends on R alone (chunks of 64 trajectories).  stop[r] is 0 or a
+kanode_train_stop; a stopped trajectory does not throw: its column of dp_rows, its loss_rows entry, loss and dp are NaN.
+Float64 handles only; up to 65536 trajectories per call.  Covered: trajectories_gradient_supported(h).  The handle's L1
+penalty is not read."""
+function trajectories_gradient(h::Handle, u0::AbstractMatrix, tspan, p::AbstractVector, saveat::AbstractVector,
+                               target::AbstractArray{<:Real,3}; kw...)
+    checkp(h, p)
+    checku(h, u0, h.nin, "u0")
+    h.nin == h.nout || throw(ArgumentError("an ODE RHS needs a chain with in_dims == out_dims"))
+    T = h.T
+    T == Float64 || throw(ArgumentError("trajectories_gradient: Float64 handles only"))
+    R = size(u0, 2)
+    1 <= R <= 65536 || throw(ArgumentError("trajectories_gradient: 1 <= R <= 65536 trajectories"))
+    ts = Vector{Float64}(saveat)
+    (issorted(ts) && !isempty(ts)) || throw(ArgumentError("saveat must be ascending and not empty"))
+    size(target) == (h.nin, R, length(ts)) ||
+        throw(DimensionMismatch("target is $(size(target)); expected $((h.nin, R, length(ts)))"))
+    trajectories_gradient_supported(h) || throw(ArgumentError("trajectories_gradient: not covered for this handle"))
+    opt = options(; kw...)
+    pd, ud, xd = upload(tohost(T, p)), upload(tohost(T, u0)), upload(tohost(T, target))
+    dp, rows, lrows = zeros(T, h.P), zeros(T, h.P, R), zeros(T, R)
+    dpd, rowsd, lrowsd = upload(dp), upload(rows), upload(lrows)
+    loss = Ref{Float64}(NaN)
+    fst = Vector{SolveStats}(undef, R)
+    ast = Vector{SolveStats}(undef, R)
+    stop = zeros(Int32, R)
+    st = GC.@preserve ts fst ast stop ccall(sym(:kanode_trajectories_gradient_tsit5), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float64}, Int64, Ptr{Cvoid},
+         Ref{SolverOptions}, Ref{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+         Ptr{SolveStats}, Ptr{SolveStats}, Ptr{Int32}, Ptr{Cvoid}),
+        h.ptr, pd.ptr, ud.ptr, R, tspan[1], tspan[2], ts, length(ts), xd.ptr, opt, loss, dpd.ptr, rowsd.ptr,
+        lrowsd.ptr, C_NULL, C_NULL, fst, ast, stop, C_NULL)
+    check(h, st)
+    download!(dp, dpd)
+    download!(rows, rowsd)
+    download!(lrows, lrowsd)
+    return loss[], dp, rows, lrows, fst, ast, stop
+end
+
 # --- pruning a sparsified KAN (LV_driver_KANODE.jl:52-108): per-edge scores on the device, the keep rule and the
 # parameter slicing on the host.  Scores are Julia [O, I] matrices (the memory kanode_edge_scores writes).
 layer_length(h::Handle, i::Integer) = Int(ccall(sym(:kanode_layer_param_length), Int64, (Ptr{Cvoid}, Int32), h.ptr, i))

@@ -2,7 +2,7 @@
 // chain has the small-chain shape, which specialisation of the kernel serves it, and for the one-workgroup adjoint
 // which model runs it, on how many threads, in how much dynamic LDS and with the dense output staged or not.
 //
-// Every launcher of kan_col.hip, kan_train.hip, kan_train_wg.hip, kan_ens_solve.hip and kan_traj_solve.hip asks here, so the ensemble
+// Every launcher of kan_col.hip, kan_train.hip, kan_train_wg.hip, kan_ens_solve.hip, kan_traj_solve.hip and kan_traj_grad.hip asks here, so the ensemble
 // entries accept exactly the shapes the single launchers accept and the training loops carve LDS exactly as the
 // adjoint launcher does.  LC is the layer-constants type (kan::LayerConst; a test passes its own struct with the
 // same field names).  The numbers that belong to the device classes come in through ChainLimits, which kan_col.hip

@@ -1,5 +1,6 @@
 // kan_ensemble.hpp — the host side of an ensemble launch of the device-resident training loops (host only, no
-// HIP): where each replica's blocks lie in the handle's training buffer, and the per-replica argument structs.
+// HIP; the constexpr index functions of the trajectory gradient are also what its kernel calls): where each
+// replica's blocks lie in the handle's training buffer, and the per-replica argument structs.
 //
 // The buffer of a launch of R replicas:
 //     out [R][2] int64 | rec [R][rec_stride bytes] | args [R] | meta | 64 spare bytes
@@ -163,5 +164,82 @@ inline size_t traj_solve_save_elem(int64_t si, int64_t r, int64_t R, int64_t N, 
 }
 // one-wave workgroups of a launch of R trajectories
 inline int64_t traj_solve_waves(int64_t R) { return (R + kTrajPerWave - 1) / kTrajPerWave; }
+
+// ---- the trajectory gradient (kanode_trajectories_gradient_tsit5, kan_traj_grad.hip) -----------------------------
+// R solves, losses and adjoints of one problem at one p from R initial conditions, one workgroup per trajectory, then
+// the mean of the R rows in a fixed order.  The caller's arrays are the trajectory solve's: u0 [R][N], target and
+// u_save [n_save][R][N].  (constexpr: the kernel states its indices with the same functions.)
+//
+// A call runs its R trajectories as consecutive launch groups of at most G.  The handle's buffer of a call:
+//     status [R][8] int64 | loss, 1 double | part [chunks(R)][P + 1] | rows [G][P + 1] | blocks [G][block stride] | meta
+// every block at a multiple of 64 bytes; status and loss are adjacent, so one copy brings both to the host.
+// status[r]: the forward's naccept, nreject, nf, status, then the adjoint's four (all zero where it did not run;
+// its status word is kTrajGradAdjointSkipped where the loss was not finite).  rows[r - g0] of a group: the gradient
+// row, the trajectory's MSE in column P.  blocks[r - g0]: the trajectory's private block,
+//     dense output [cap][7][N] | k1_0 [N] | u_save / dl [n_save][N] | target[:, r, :] gathered [n_save][N]
+// meta: saveat [n_save] | stops [nstops] (doubles), joff [nstops + 2] | jrows (int32): one copy for all.
+constexpr int kTrajGradStatusWords = 8;
+constexpr int64_t kTrajGradAdjointSkipped = 2;
+constexpr int64_t kTrajGradMax = 65536;   // trajectories of one call (kTrajMaxTrajectories)
+constexpr size_t traj_grad_row_elems(int64_t P) { return (size_t)P + 1; }
+constexpr size_t traj_grad_status_word(int64_t r) { return (size_t)r * kTrajGradStatusWords; }
+constexpr size_t traj_grad_u0_elem(int64_t r, int64_t N, int64_t j) { return (size_t)r * (size_t)N + (size_t)j; }
+constexpr size_t traj_grad_save_elem(int64_t si, int64_t r, int64_t R, int64_t N, int64_t j) {
+    return ((size_t)si * (size_t)R + (size_t)r) * (size_t)N + (size_t)j;
+}
+// a private block, in doubles from its start
+constexpr size_t traj_grad_block_usave(int64_t N, int64_t cap) { return (size_t)(cap * 7 + 1) * (size_t)N; }
+constexpr size_t traj_grad_block_target(int64_t N, int64_t cap, int64_t n_save) {
+    return traj_grad_block_usave(N, cap) + (size_t)n_save * (size_t)N;
+}
+constexpr size_t traj_grad_block_elems(int64_t N, int64_t cap, int64_t n_save) {
+    return traj_grad_block_target(N, cap, n_save) + (size_t)n_save * (size_t)N;
+}
+// The summation order of the reduction, a function of R alone: chunk c holds the trajectories
+// [chunk_begin(c), chunk_end(c, R)), kTrajGradChunk consecutive ones (the last chunk fewer).  A chunk is summed from
+// 0.0 in ascending r, the chunk sums from 0.0 in ascending c, then one division by R.
+constexpr int kTrajGradChunk = 64;
+constexpr int64_t traj_grad_chunks(int64_t R) { return (R + kTrajGradChunk - 1) / kTrajGradChunk; }
+constexpr int64_t traj_grad_chunk_begin(int64_t c) { return c * kTrajGradChunk; }
+constexpr int64_t traj_grad_chunk_end(int64_t c, int64_t R) {
+    return (c + 1) * kTrajGradChunk < R ? (c + 1) * kTrajGradChunk : R;
+}
+struct TrajGradLayout {
+    size_t off_loss, off_part, off_rows, off_blocks, block_stride, off_meta, bytes;
+};
+// R trajectories in the call, at most G in a launch group
+inline TrajGradLayout traj_grad_layout(int64_t R, int64_t G, int64_t P, size_t block_bytes, size_t meta_bytes) {
+    TrajGradLayout L;
+    const size_t row = traj_grad_row_elems(P) * sizeof(double);
+    L.off_loss = (size_t)R * kTrajGradStatusWords * sizeof(int64_t);
+    L.off_part = ensemble_round(L.off_loss + sizeof(double));
+    L.off_rows = ensemble_round(L.off_part + (size_t)traj_grad_chunks(R) * row);
+    L.off_blocks = ensemble_round(L.off_rows + (size_t)G * row);
+    L.block_stride = ensemble_round(block_bytes);
+    L.off_meta = L.off_blocks + (size_t)G * L.block_stride;
+    L.bytes = ensemble_round(L.off_meta + meta_bytes) + 64;
+    return L;
+}
+// the host copy of a call: the status words and the loss
+inline size_t traj_grad_host_bytes(int64_t R) {
+    return (size_t)R * kTrajGradStatusWords * sizeof(int64_t) + sizeof(double);
+}
+// what one more trajectory of a launch group adds to the buffer
+inline size_t traj_grad_bytes_per_traj(int64_t P, size_t block_bytes) {
+    return ensemble_round(block_bytes) + traj_grad_row_elems(P) * sizeof(double);
+}
+// The trajectories of one launch group: the most whose buffer stays within `budget` whatever R the call has (the
+// status words and chunk sums are counted at kTrajGradMax), at most kTrajGradMax.  A multiple of kTrajGradChunk, so a
+// chunk never straddles two groups and the chunk sums of a group can be formed right after its launch; 0 where not
+// even one chunk fits.
+inline int64_t traj_grad_group(int64_t P, size_t block_bytes, size_t meta_bytes, size_t budget) {
+    const size_t fixed = traj_grad_layout(kTrajGradMax, 0, P, 0, meta_bytes).bytes + 128;
+    if (budget <= fixed) return 0;
+    int64_t G = (int64_t)((budget - fixed) / traj_grad_bytes_per_traj(P, block_bytes));
+    if (G > kTrajGradMax) G = kTrajGradMax;
+    return G - G % kTrajGradChunk;
+}
+// the chain adjoint's meta block for this saveat list, as an upper bound (ensemble_meta_bound without a test problem)
+inline size_t traj_grad_meta_bound(int64_t n_save) { return ensemble_meta_bound(n_save, 0); }
 
 }  // namespace kan

@@ -662,6 +662,37 @@ bool chain_tsit5_traj_supported(const LayerConst* hlcs, int nl, int64_t P, size_
 template <typename T>
 hipError_t launch_kd_chain_tsit5_traj(const LayerConst* hlcs, int nl, const LayerConst* lcs, const T* p, int64_t P,
                                       const T* u0, int64_t R, const ChainSolveArgs& a, hipStream_t st);
+// The trajectory gradient (kan_traj_grad.hip; kanode_trajectories_gradient_tsit5): R (<= kTrajMaxTrajectories)
+// trajectories of one small fp64 chain at one p, workgroup r (one wave) running kd_chain_train_wg_kernel's phases A
+// and B once at B = 1 from u0[r] against target[:, r, :], the adjoint always on ChainModel (chain_adjoint_plan with
+// wide = false).  t: what all share (the solver options, p, n_save, the device saveat list, the jump groups, cap,
+// dl_lds, dl_scale = 2 / (n_save·N), B = 1, N; stage_rec, n_save_test, act_reg and the Adam fields zero; u0, target,
+// rec, loss and out are set per workgroup by the kernel).  The index functions are kan_ensemble.hpp's.
+struct TrajGradArgs {
+    ChainTrainArgs t;
+    const double* u0;        // [R][N], at this launch's first trajectory
+    const double* target;    // [n_save][R_all][N], at this launch's first trajectory
+    double* u_save;          // as target, or null; the columns of a trajectory whose forward stopped are not written
+    int64_t R_all;           // trajectories of the whole call: the row stride of target and u_save
+    char* blocks;            // [R][block_stride bytes] private blocks (traj_grad_block_elems doubles used)
+    size_t block_stride;
+    double* rows;            // [R][P + 1]: the gradient row, the trajectory's MSE in column P; NaN where it stopped
+    double* dp_rows;         // [R][P] or null: this launch's rows of the caller's array
+    double* loss_rows;       // [R] or null
+    double* du0;             // [R][N] or null
+    int64_t* status;         // [R][8]: the forward's naccept, nreject, nf, status, then the adjoint's
+};
+// the shapes covered: chain_train_wg_supported at B = 1 with wide = false
+bool chain_traj_grad_supported(const LayerConst* hlcs, int nl, int64_t P, size_t esize);
+// the dynamic LDS of a launch (0: does not fit); *dl_lds as chain_train_wg_lds reports it
+size_t chain_traj_grad_lds(const LayerConst* hlcs, int nl, int64_t P, int64_t cap, int64_t n_save, int* dl_lds);
+hipError_t launch_kd_chain_traj_grad(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P,
+                                     const TrajGradArgs& g, int64_t R, hipStream_t st);
+// The reduction of the rows in kan_ensemble.hpp's chunk order, two launches: part [chunks(R)][P + 1] from rows
+// [R][P + 1] (a launch group's rows give its own chunks: a group's first trajectory is a multiple of the chunk), then
+// dp [P] and *loss from all chunks(R) sums, divided by R.
+hipError_t launch_traj_grad_chunks(const double* rows, int64_t R, int64_t P, double* part, hipStream_t st);
+hipError_t launch_traj_grad_total(const double* part, int64_t R, int64_t P, double* dp, double* loss, hipStream_t st);
 
 // surrogate shapes (kan_wide.hip)
 constexpr int kWideKT = 8;       // column tile of the wide-out kernels

@@ -2,7 +2,8 @@
 // one-workgroup forward and adjoint cover that kan_train.hip's Lotka-Volterra kernel does not: a pruned [2,k,2],
 // a [3,6,3] chain, three layers, up to kChainSolveMaxBatch trajectories (KANODE_OPT_TRAIN_ANY_CHAIN), and its ensemble
 // twin, R such loops in one launch, one workgroup each (kanode_fit_ensemble_tsit5).  The loop's text is
-// kan_train_wg_body.inc, included into both kernels.
+// kan_train_wg_body.inc, included into both kernels; the phase functions are kan_train_wg_phases.hpp, shared with
+// kan_traj_grad.hip.
 //
 // The loop is LV_driver_KANODE.jl:279-291, as in kan_train.hip; here every phase runs on the whole workgroup, with
 // the device functions of the two-launch path (kan_onewg.hpp on the model classes of kan_col.hip).  Per iteration it:
@@ -29,193 +30,9 @@
 #define KAN_COL_DEVICE_ONLY
 #include "kan_col.hip"
 #include "kan_train_loss.hpp"
+#include "kan_train_wg_phases.hpp"
 
 namespace kan {
-
-enum TrainWgModel : int { kWgNone = 0, kWgChain = 1, kWgWide = 2 };
-
-// LDS of a launch, in doubles after the layer constants: ps [P] | work (ChainModel: rows [NG][P]; WideModel: its
-// scratch) | μ [2][P] | kμ [7][P] | the gradient [P] | ts, dts [cap] each | saveat [n_save] | the test saveat
-// [n_save_test] | (dl_lds) u_save / dl [n_save][n], the test u_save [n_save_test][n] | (stage_rec) the dense output
-// [(7 cap + 1) n].  work, μ and kμ are contiguous (zeroed together, as the adjoint kernels do).
-struct TrainWgCarve {
-    size_t ps, work, mu, km, gl, tsl, dtsl, sv, svt, dl, ust, recl, total;   // doubles, from the end of the constants
-};
-__host__ __device__ inline TrainWgCarve train_wg_carve(int64_t P, int64_t work, int64_t cap, int64_t n_save,
-                                                       int64_t n_save_test, int64_t n, int dl_lds, int stage_rec) {
-    TrainWgCarve c{};
-    size_t o = 0;
-    c.ps = o, o += P;
-    c.work = o, o += work;
-    c.mu = o, o += 2 * P;
-    c.km = o, o += 7 * P;
-    c.gl = o, o += P;
-    c.tsl = o, o += cap;
-    c.dtsl = o, o += cap;
-    c.sv = o, o += n_save;
-    c.svt = o, o += n_save_test;
-    c.dl = o, o += dl_lds ? n_save * n : 0;
-    c.ust = o, o += dl_lds ? n_save_test * n : 0;
-    c.recl = o, o += stage_rec ? (cap * 7 + 1) * n : 0;
-    c.total = o;
-    return c;
-}
-
-// what every phase needs besides the launch's arguments: pointers into LDS, typed as such (a phase is a function of
-// its own, and through a plain pointer argument it would read LDS with flat loads), and the global dense-output block
-#define KAN_LDS __attribute__((address_space(3)))
-struct TrainWgPtrs {
-    KAN_LDS const double* tab;       // the exp table
-    KAN_LDS const LayerConst* lcl;
-    KAN_LDS double *ps, *work, *mu, *km, *gl, *tsl, *dtsl, *sv, *svt, *recl;
-    double *dl, *ust;        // u_save / dl and the test u_save: LDS (dl_lds) or global
-    double *rec, *rk1;       // global: [cap][7][n], k1_0 [n]
-    KAN_LDS double* red;     // onewg_bsum's partials
-    KAN_LDS int64_t* fo;     // [3][4]: the counters of the training forward, the test solve, the adjoint
-    KAN_LDS double* lossv;   // loss[it]
-    int nl, P;
-};
-
-// A value every lane holds alike, moved to scalar registers.  The phases read their arguments from private memory
-// (structs passed by reference to functions that are not inlined), where the compiler cannot know that they are
-// wave-uniform: without this every solver option is a vector register and every step-control branch a vector branch.
-template <typename T>
-__device__ __forceinline__ T wg_uniform(T v) {
-    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two scalar registers");
-    int x[sizeof(T) / 4];
-    __builtin_memcpy(x, &v, sizeof(T));
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(T) / 4); ++i) x[i] = __builtin_amdgcn_readfirstlane(x[i]);
-    __builtin_memcpy(&v, x, sizeof(T));
-    return v;
-}
-
-// A: the solve at p_it over (t0, tf), dense output kept, or (tst) the test solve over (t0, tf_test)
-template <int FN, int PATH, class FS>
-__device__ __noinline__ void wg_forward(const ChainTrainArgs& a, const TrainWgPtrs& L, bool tst_) {
-    const bool tst = wg_uniform((int)tst_) != 0;
-    ChainSolveArgs fa{};
-    fa.t0 = wg_uniform(a.t0);
-    fa.tf = wg_uniform(tst ? a.tf_test : a.tf);
-    fa.dt = wg_uniform(a.dt);
-    fa.abstol = wg_uniform(a.abstol);
-    fa.reltol = wg_uniform(a.reltol);
-    fa.dtmin = wg_uniform(a.dtmin);
-    fa.beta1 = wg_uniform(a.beta1);
-    fa.beta2 = wg_uniform(a.beta2);
-    fa.gamma = wg_uniform(a.gamma);
-    fa.qmin = wg_uniform(a.qmin);
-    fa.qmax = wg_uniform(a.qmax);
-    fa.qoldinit = wg_uniform(a.qoldinit);
-    fa.adaptive = wg_uniform(a.adaptive);
-    fa.maxiters = wg_uniform(a.maxiters);
-    fa.n_save = wg_uniform(tst ? a.n_save_test : a.n_save);
-    fa.cap = wg_uniform(a.cap);
-    fa.saveat = (const double*)wg_uniform(tst ? L.svt : L.sv);
-    fa.u_save = wg_uniform(tst ? L.ust : L.dl);
-    fa.rec = wg_uniform(tst ? (double*)nullptr : L.rec);
-    fa.k1_0 = wg_uniform(L.rk1);
-    fa.ts = (double*)wg_uniform(L.tsl);
-    fa.dts = (double*)wg_uniform(L.dtsl);
-    fa.out = (int64_t*)wg_uniform(L.fo) + (tst ? 4 : 0);
-    const Math<double> M{(const double*)wg_uniform(L.tab)};
-    const int N = wg_uniform((int)a.N), nl = wg_uniform(L.nl), P = wg_uniform(L.P);
-    const int64_t B = wg_uniform(a.B);
-    const int j = threadIdx.x & (kChainDim - 1);
-    const int64_t col = threadIdx.x / kChainDim;
-    ChainModel<double, FN, PATH, FS> m{M, (const LayerConst*)wg_uniform(L.lcl), nl, (const double*)wg_uniform(L.ps),
-                                       nullptr, P, j, 0, col < B && j < N, (int64_t)N * col + j, (int64_t)N * B};
-    onewg_tsit5<double>(m, wg_uniform(a.u0), fa, (double*)wg_uniform(L.red));
-}
-
-// A: loss[it] and the cotangent in place of u_save, on wave 0
-__device__ __noinline__ void wg_loss(const ChainTrainArgs& a, const TrainWgPtrs& L, int64_t it) {
-    if (threadIdx.x >= kWave) return;
-    double lv = wave_mse<true>(L.dl, a.target, a.n_save * a.N * a.B, a.dl_scale);
-    if (a.act_reg != 0.0) lv = l1_loss(lv, (const double*)L.ps, L.P, a.act_reg);   // (λ = 0: not one operation more)
-    if (threadIdx.x == 0) {
-        a.loss[it] = lv;
-        *L.lossv = lv;
-    }
-}
-
-// A: loss_test[it - 1] from the test solve just run, on wave 0
-__device__ __noinline__ void wg_test_loss(const ChainTrainArgs& a, const TrainWgPtrs& L, int64_t it) {
-    if (threadIdx.x >= kWave) return;
-    const double lt = wave_mse<false>(L.ust, a.target_test, a.n_save_test * a.N * a.B, 0.0);
-    if (threadIdx.x == 0) a.loss_test[it - 1] = L.fo[7] == 0 ? lt : __longlong_as_double(0x7ff8000000000000LL);
-}
-
-// (the generic shapes are too large for the stage loops to be unrolled, as in kan_col.hip's adjoint kernels)
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wpass-failed"
-// B: the InterpolatingAdjoint from the dense output just written; the gradient -> L.gl, the counters -> L.fo[8..]
-// ADJ: kWgChain (ChainModel<FN, PATH, FS>, as kd_chain_adjoint_kernel) or kWgWide (WideModel<WN>, as
-// kd_chain_adjoint_wide_kernel)
-template <int ADJ, int WN, int FN, int PATH, class FS>
-__device__ __noinline__ void wg_adjoint(const ChainTrainArgs& a, const TrainWgPtrs& L) {
-    ChainAdjointArgs aa{};
-    aa.t0 = wg_uniform(a.t0);
-    aa.tf = wg_uniform(a.tf);
-    aa.dt = wg_uniform(a.dt);
-    aa.abstol = wg_uniform(a.abstol);
-    aa.reltol = wg_uniform(a.reltol);
-    aa.dtmin = wg_uniform(a.dtmin);
-    aa.beta1 = wg_uniform(a.beta1);
-    aa.beta2 = wg_uniform(a.beta2);
-    aa.gamma = wg_uniform(a.gamma);
-    aa.qmin = wg_uniform(a.qmin);
-    aa.qmax = wg_uniform(a.qmax);
-    aa.qoldinit = wg_uniform(a.qoldinit);
-    aa.adaptive = wg_uniform(a.adaptive);
-    aa.maxiters = wg_uniform(a.maxiters);
-    aa.rec = wg_uniform(L.rec);
-    aa.k1_0 = wg_uniform(L.rk1);
-    aa.ts = (const double*)wg_uniform(L.tsl);
-    aa.dts = (const double*)wg_uniform(L.dtsl);
-    aa.nsteps = wg_uniform(L.fo[0]);
-    aa.dl_du = wg_uniform(L.dl);
-    aa.stops = wg_uniform(a.stops);
-    aa.nstops = wg_uniform(a.nstops);
-    aa.jrows = wg_uniform(a.jrows);
-    aa.joff = wg_uniform(a.joff);
-    aa.dp = (double*)wg_uniform(L.gl);
-    aa.out = (int64_t*)wg_uniform(L.fo) + 8;
-    const Math<double> M{(const double*)wg_uniform(L.tab)};
-    double* const mu = (double*)wg_uniform(L.mu);
-    double* const km = (double*)wg_uniform(L.km);
-    double* const work = (double*)wg_uniform(L.work);
-    const double* const tsl = (const double*)wg_uniform(L.tsl);
-    const double* const dtsl = (const double*)wg_uniform(L.dtsl);
-    const LayerConst* const lcl = (const LayerConst*)wg_uniform(L.lcl);
-    const double* const ps = (const double*)wg_uniform(L.ps);
-    double* const red = (double*)wg_uniform(L.red);
-    const int64_t B = wg_uniform(a.B);
-    const int nl = wg_uniform(L.nl), stage_rec = wg_uniform(a.stage_rec);
-    const int N = wg_uniform((int)a.N), P = wg_uniform(L.P);
-    if constexpr (ADJ == kWgWide) {
-        for (int i = threadIdx.x; i < WideModel<double, WN>::kEnd + 9 * P; i += blockDim.x) work[i] = 0.0;
-        __syncthreads();
-        double* recl = nullptr;
-        if (stage_rec) {
-            recl = (double*)wg_uniform(L.recl);
-            onewg_stage_rec<double>(recl, aa, N);
-        }
-        WideModel<double, WN> m{M, lcl, ps, work, P, (int)threadIdx.x < N, (int64_t)threadIdx.x, (int64_t)N};
-        onewg_adjoint<double>(m, aa, mu, km, tsl, dtsl, red, recl);
-    } else {
-        const int NG = blockDim.x / kChainDim;
-        const int NGa = B < NG ? (int)B : NG;   // groups holding a trajectory
-        for (int i = threadIdx.x; i < NG * P + 9 * P; i += blockDim.x) work[i] = 0.0;
-        __syncthreads();
-        const int j = threadIdx.x & (kChainDim - 1);
-        const int64_t col = threadIdx.x / kChainDim;
-        ChainModel<double, FN, PATH, FS> m{M, lcl, nl, ps, work, P, j, NGa, col < B && j < N, (int64_t)N * col + j,
-                                           (int64_t)N * B};
-        onewg_adjoint<double>(m, aa, mu, km, tsl, dtsl, red);
-    }
-}
-#pragma clang diagnostic pop
 
 // C: the records and Adam, parameter q on thread q mod blockDim
 __device__ __noinline__ void wg_adam(const ChainTrainArgs& a, const TrainWgPtrs& L, int64_t it, double bp1, double bp2) {

@@ -74,6 +74,10 @@ struct kanode_handle {
     // copy of the status words.  Grow-only; kanode_reserve does not cover them.
     kan::DevBuf traj_solve_buf;
     kan::PinnedBuf traj_solve_host;
+    // the trajectory gradient (kanode_trajectories_gradient_tsit5; kan_ensemble.hpp's TrajGradLayout), and the host
+    // copy of its status words and loss.  Grow-only, at most kEnsembleBudget; kanode_reserve does not cover them.
+    kan::DevBuf traj_grad_buf;
+    kan::PinnedBuf traj_grad_host;
     // table reuse inside one integrator solve (p constant): build each table set once
     bool hold_tables = false;
     bool built_phi = false, built_vjp = false;

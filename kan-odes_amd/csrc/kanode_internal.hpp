@@ -17,6 +17,7 @@ namespace kan {
 struct ChainSolveArgs;
 struct ChainAdjointArgs;
 struct ChainTrainArgs;
+struct TrajGradArgs;
 struct EnsembleReplicas;
 struct AdjStepArgs;
 struct PairAdjArgs;
@@ -204,6 +205,20 @@ int64_t kanode_internal_fit_ensemble_group(const kanode_handle* h, int64_t batch
 kanode_status kanode_internal_chain_fit_ensemble(kanode_handle* h, int64_t batch, kan::ChainTrainArgs* a,
                                                  const kan::EnsembleReplicas* ens, const std::vector<char>& meta,
                                                  int64_t* res, void* stream);
+// kanode_trajectories_gradient_tsit5 (kd_chain_traj_grad_kernel and the two reduction launches, kan_traj_grad.hip).
+// _ok: fp64 chains the one-workgroup solve runs at batch 1 that kd_chain_train_wg_kernel covers at B = 1 on the
+// ChainModel adjoint (whatever KANODE_OPT_CHAIN_WIDE says).  _group: the trajectories of one launch for this problem
+// (kan_ensemble.hpp's traj_grad_group at the 256 MiB budget; 0: not covered or no fit in LDS).  The call: g->t holds
+// the options, p, n_save, dl_scale and nstops, g's arrays are the caller's whole arrays (R trajectories); the
+// capacity, the LDS flags, the buffer and meta pointers and the per-group offsets are set here.  meta = saveat
+// [n_save] | stops [nstops] (doubles), then joff [nstops + 2] | jrows (int32).  Runs consecutive groups, then the
+// total; one copy of the status words and the loss, one synchronise.  res = [R][8], *loss the total, dp device [P].
+bool kanode_internal_traj_grad_ok(const kanode_handle* h);
+int64_t kanode_internal_traj_grad_group(const kanode_handle* h, bool adaptive, double t0, double tf, double dt,
+                                        int64_t n_save);
+kanode_status kanode_internal_traj_grad(kanode_handle* h, kan::TrajGradArgs* g, int64_t R,
+                                        const std::vector<char>& meta, int64_t* res, double* loss, double* dp,
+                                        void* stream);
 // the device-resident Fisher-KPP training loop on the forward-mode gradient (fk_small_train_kernel,
 // kanode_train_forward_tsit5): whether the handle takes it at this batch (with_test: with the logged-loss solve),
 // and one launch.  meta = saveat [n_save] | saveat_test [n_save_test] (doubles), kept on the handle with the two

@@ -4,6 +4,7 @@
 #include "kanode.h"
 
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -104,9 +105,9 @@ struct TrainWgFit {
     int dl_lds, stage_rec;
     size_t rec_bytes;   // the private global block (ChainTrainArgs::rec), a multiple of 64 bytes
 };
-static bool chain_train_wg_fit(const kanode_handle* h, int64_t batch, bool adaptive, double t0, double tf, double dt,
-                               int64_t n_save, int64_t n_save_test, TrainWgFit& f) {
-    const bool wide = h->opt.chain_wide;
+// (wide: the adjoint's model is chosen with it; the trajectory gradient passes false, the loops the handle's option)
+static bool chain_train_wg_fit(const kanode_handle* h, int64_t batch, bool wide, bool adaptive, double t0, double tf,
+                               double dt, int64_t n_save, int64_t n_save_test, TrainWgFit& f) {
     auto lds = [&](int64_t cap, int* dl, int* sr) {
         return kan::chain_train_wg_lds(h->hlc, h->n_layers, h->P, batch, wide, cap, n_save, n_save_test, dl, sr);
     };
@@ -139,7 +140,8 @@ static kanode_status chain_train_wg(kanode_handle* h, const char* what, int64_t 
                                     const kan::EnsembleReplicas* ens, const std::vector<char>& meta, int64_t* res,
                                     hipStream_t st) {
     TrainWgFit f{};
-    if (!chain_train_wg_fit(h, batch, a->adaptive != 0, a->t0, a->tf, a->dt, a->n_save, a->n_save_test, f))
+    if (!chain_train_wg_fit(h, batch, h->opt.chain_wide, a->adaptive != 0, a->t0, a->tf, a->dt, a->n_save,
+                            a->n_save_test, f))
         return fail(h, KANODE_ERR_UNSUPPORTED, std::string(what) + ": not supported (the problem does not fit one workgroup's LDS)");
     const bool wide = h->opt.chain_wide;
     a->cap = f.cap;
@@ -159,7 +161,7 @@ int64_t kanode_internal_fit_ensemble_group(const kanode_handle* h, int64_t batch
                                            double dt, int64_t n_save, int64_t n_save_test) {
     TrainWgFit f{};
     if (batch < 1 || n_save < 1 || n_save_test < 0 || !(tf > t0) || !kanode_internal_fit_ensemble_ok(h, batch) ||
-        !chain_train_wg_fit(h, batch, adaptive, t0, tf, dt, n_save, n_save_test, f))
+        !chain_train_wg_fit(h, batch, h->opt.chain_wide, adaptive, t0, tf, dt, n_save, n_save_test, f))
         return 0;
     return kan::ensemble_group(kan::kTrainMaxReplicas, f.rec_bytes, sizeof(kan::ChainTrainArgs),
                                kan::ensemble_meta_bound(n_save, n_save_test), kan::kEnsembleBudget);
@@ -221,6 +223,102 @@ kanode_status kanode_internal_chain_train(kanode_handle* h, int64_t batch, kan::
                                                                                dargs, R, st)
                                          : kan::launch_kd_chain_train(h->hlc, h->n_layers, h->dlc(), h->P, a0, st);
                         });
+}
+
+// ---- the trajectory gradient (kan_traj_grad.hip) ----
+bool kanode_internal_traj_grad_ok(const kanode_handle* h) {
+    return h->spec.dtype == KANODE_F64 && h->spec.rhs_kind == KANODE_RHS_CHAIN && h->n_in == h->n_out &&
+           kanode_internal_chain_tsit5_ok(h, 1) &&
+           kan::chain_traj_grad_supported(h->hlc, h->n_layers, h->P, h->esize);
+}
+// the capacity by kanode_fit_ensemble_tsit5's rules at batch 1 on the ChainModel adjoint, and a trajectory's block
+static bool traj_grad_fit(const kanode_handle* h, bool adaptive, double t0, double tf, double dt, int64_t n_save,
+                          TrainWgFit& f, size_t& block_bytes) {
+    if (n_save < 1 || !(tf > t0) || !kanode_internal_traj_grad_ok(h) ||
+        !chain_train_wg_fit(h, 1, false, adaptive, t0, tf, dt, n_save, 0, f) || f.stage_rec)
+        return false;
+    block_bytes = sizeof(double) * kan::traj_grad_block_elems(h->n_in, f.cap, n_save);
+    return true;
+}
+int64_t kanode_internal_traj_grad_group(const kanode_handle* h, bool adaptive, double t0, double tf, double dt,
+                                        int64_t n_save) {
+    TrainWgFit f{};
+    size_t block_bytes = 0;
+    if (!traj_grad_fit(h, adaptive, t0, tf, dt, n_save, f, block_bytes)) return 0;
+    return kan::traj_grad_group(h->P, block_bytes, kan::traj_grad_meta_bound(n_save), kan::kEnsembleBudget);
+}
+kanode_status kanode_internal_traj_grad(kanode_handle* h, kan::TrajGradArgs* g, int64_t R,
+                                        const std::vector<char>& meta, int64_t* res, double* loss, double* dp,
+                                        void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    const std::string what = "kanode_trajectories_gradient_tsit5";
+    kan::ChainTrainArgs& a = g->t;
+    TrainWgFit f{};
+    size_t block_bytes = 0;
+    if (!traj_grad_fit(h, a.adaptive != 0, a.t0, a.tf, a.dt, a.n_save, f, block_bytes))
+        return fail(h, KANODE_ERR_UNSUPPORTED, what + ": not supported (the problem does not fit one workgroup's LDS)");
+    const int64_t G = kan::traj_grad_group(h->P, block_bytes, kan::traj_grad_meta_bound(a.n_save), kan::kEnsembleBudget);
+    if (G < 1 || meta.size() > kan::traj_grad_meta_bound(a.n_save))
+        return fail(h, KANODE_ERR_UNSUPPORTED, what + ": not supported (a launch group does not fit the handle's buffer)");
+    const int64_t Gn = std::min(R, G);
+    const kan::TrajGradLayout L = kan::traj_grad_layout(R, Gn, h->P, block_bytes, meta.size());
+    const size_t host_bytes = kan::traj_grad_host_bytes(R);
+    if (h->traj_grad_buf.bytes() < L.bytes || h->traj_grad_host.bytes() < host_bytes) {
+        HIP_TRY(h, hipStreamSynchronize(st));   // (an earlier call's kernels may still use the old buffers)
+        if (h->traj_grad_buf.reserve(L.bytes) != hipSuccess || h->traj_grad_host.reserve(host_bytes) != hipSuccess)
+            return fail(h, KANODE_ERR_ALLOC, what + ": out of memory for the trajectories' blocks");
+    }
+    char* const base = h->traj_grad_buf.as<char>();
+    // (the call synchronises before it returns, so the caller's bytes outlive the copy)
+    HIP_TRY(h, hipMemcpyAsync(base + L.off_meta, meta.data(), meta.size(), hipMemcpyHostToDevice, st));
+    const double* md = (const double*)(base + L.off_meta);
+    a.saveat = md;
+    a.saveat_test = nullptr;
+    a.stops = md + a.n_save;
+    a.joff = (const int32_t*)(a.stops + a.nstops);
+    a.jrows = a.joff + a.nstops + 2;
+    a.cap = f.cap;
+    a.dl_lds = f.dl_lds;
+    a.stage_rec = 0;
+    a.B = 1;
+    a.N = h->n_in;
+    const kan::TrajGradArgs all = *g;
+    const size_t N = (size_t)h->n_in, P = (size_t)h->P;
+    double* const part = (double*)(base + L.off_part);
+    double* const dloss = (double*)(base + L.off_loss);
+    // consecutive groups of G trajectories, one launch and its chunk sums each, in stream order (they share the
+    // rows and the blocks); G is a multiple of the chunk, so a group's chunks are whole
+    for (int64_t g0 = 0; g0 < R; g0 += G) {
+        const int64_t Rg = std::min(G, R - g0);
+        kan::TrajGradArgs gg = all;
+        gg.u0 = all.u0 + (size_t)g0 * N;
+        gg.target = all.target + (size_t)g0 * N;
+        gg.u_save = all.u_save ? all.u_save + (size_t)g0 * N : nullptr;
+        gg.R_all = R;
+        gg.blocks = base + L.off_blocks;
+        gg.block_stride = L.block_stride;
+        gg.rows = (double*)(base + L.off_rows);
+        gg.dp_rows = all.dp_rows ? all.dp_rows + (size_t)g0 * P : nullptr;
+        gg.loss_rows = all.loss_rows ? all.loss_rows + g0 : nullptr;
+        gg.du0 = all.du0 ? all.du0 + (size_t)g0 * N : nullptr;
+        gg.status = (int64_t*)base + kan::traj_grad_status_word(g0);
+        hipError_t e = kan::launch_kd_chain_traj_grad(h->hlc, h->n_layers, h->dlc(), h->P, gg, Rg, st);
+        if (e == hipErrorNotSupported)
+            return fail(h, KANODE_ERR_UNSUPPORTED, what + ": not supported (shape or saveat list not covered by the "
+                                                          "one-workgroup kernel)");
+        if (e == hipSuccess)
+            e = kan::launch_traj_grad_chunks(gg.rows, Rg, h->P,
+                                             part + (size_t)(g0 / kan::kTrajGradChunk) * kan::traj_grad_row_elems(h->P), st);
+        if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, what + " launch: " + hipGetErrorString(e));
+    }
+    if (const hipError_t e = kan::launch_traj_grad_total(part, R, h->P, dp, dloss, st); e != hipSuccess)
+        return fail(h, KANODE_ERR_HIP, what + " reduction: " + hipGetErrorString(e));
+    HIP_TRY(h, hipMemcpyAsync(h->traj_grad_host.ptr(), base, host_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    const char* hp = h->traj_grad_host.as<char>();
+    std::memcpy(res, hp, (size_t)R * kan::kTrajGradStatusWords * sizeof(int64_t));
+    std::memcpy(loss, hp + L.off_loss, sizeof(double));
+    return KANODE_OK;
 }
 
 bool kanode_internal_fk_train_ok(const kanode_handle* h, int64_t batch, bool with_test) {

@@ -10,8 +10,8 @@ from .handle import KanodeHandle, LayerCfg
 from .layers import Chain, KDense, glorot_uniform, linrange_f32
 from .rhs import ChainRHS, FisherKPPRHS, fisher_kpp_laplacian, layer_apply, rhs_apply
 from .ode import EnsembleSolution, Solution, TrajectorySolution, Tsit5Options, solve, solve_ensemble, solve_trajectories
-from .adjoint import DenseRecord, interpolating_adjoint
-from .train import Adam, EnsembleTrainer, FusedAdam, Trainer, mse_loss, reg_loss
+from .adjoint import DenseRecord, interpolating_adjoint, trajectories_mse_gradient
+from .train import Adam, EnsembleTrainer, FusedAdam, Trainer, TrajectoryTrainer, mse_loss, reg_loss
 from .sparse import prune, prune_nodes, prune_params
 from . import checkpoint, comm, tp
 from .tp import GridShardedChainRHS
@@ -20,6 +20,6 @@ __all__ = [
     "DenseRecord", "interpolating_adjoint",
     "KanodeError", "LIB_PATH", "lib", "KanodeHandle", "LayerCfg", "Chain", "KDense", "glorot_uniform",
     "linrange_f32", "ChainRHS", "FisherKPPRHS", "fisher_kpp_laplacian", "layer_apply", "rhs_apply",
-    "Solution", "EnsembleSolution", "TrajectorySolution", "Tsit5Options", "solve", "solve_ensemble", "solve_trajectories", "Adam", "EnsembleTrainer", "FusedAdam", "Trainer", "mse_loss", "reg_loss", "checkpoint", "comm", "tp",
+    "Solution", "EnsembleSolution", "TrajectorySolution", "Tsit5Options", "solve", "solve_ensemble", "solve_trajectories", "trajectories_mse_gradient", "Adam", "EnsembleTrainer", "FusedAdam", "Trainer", "TrajectoryTrainer", "mse_loss", "reg_loss", "checkpoint", "comm", "tp",
     "GridShardedChainRHS", "prune", "prune_nodes", "prune_params",
 ]

@@ -156,6 +156,14 @@ SIGNATURES = [
     ("kanode_solve_trajectories_tsit5", C.c_int, [_H, _P, _P, C.c_int64, C.c_double, C.c_double,
                                                   C.POINTER(C.c_double), C.c_int64, _P, C.POINTER(SolverOptsC),
                                                   C.POINTER(SolveStatsC), C.POINTER(C.c_int32), _P]),
+    ("kanode_trajectories_gradient_supported", C.c_int32, [_H]),
+    ("kanode_trajectories_gradient_group", C.c_int64, [_H, C.c_double, C.c_double, C.c_int64,
+                                                       C.POINTER(SolverOptsC)]),
+    ("kanode_trajectories_gradient_tsit5", C.c_int, [_H, _P, _P, C.c_int64, C.c_double, C.c_double,
+                                                     C.POINTER(C.c_double), C.c_int64, _P, C.POINTER(SolverOptsC),
+                                                     C.POINTER(C.c_double), _P, _P, _P, _P, _P,
+                                                     C.POINTER(SolveStatsC), C.POINTER(SolveStatsC),
+                                                     C.POINTER(C.c_int32), _P]),
     ("kanode_adjoint_tsit5", C.c_int, [_H, _P, _P, _P, _P, _P, C.POINTER(SolverOptsC), C.POINTER(SolveStatsC), _P]),
     ("kanode_adjoint_step_sizes", C.c_int64, [_H, _P, C.c_int64]),
     ("kanode_table_rejections", C.c_int, [_H, _P]),

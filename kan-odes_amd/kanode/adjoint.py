@@ -352,3 +352,122 @@ def native_mse_gradient_forward(f, u0, tspan, p, saveat, opt: Tsit5Options, targ
     stats = dict(st)
     stats["sensealg"] = "forward"
     return loss, _contract(S, dl), Solution(list(saveat), u_save, stats)
+
+
+# ---- the trajectory ensemble: R initial conditions, each an ODE of its own, one loss over all ----
+
+TRAJECTORIES_GRADIENT_MAX = 65536   # trajectories of one kanode_trajectories_gradient_tsit5 call
+TRAJECTORIES_GRADIENT_CHUNK = 64    # kan_ensemble.hpp's kTrajGradChunk
+
+
+def combine_trajectory_rows(rows: torch.Tensor) -> torch.Tensor:
+    """rows [R, W] -> their mean over R [W] in the order of kanode_trajectories_gradient_tsit5, a function of R alone:
+    chunks of 64 consecutive rows summed from 0.0 in ascending r, the chunk sums summed from 0.0 in ascending chunk
+    order, one division by R; every add rounded.  (The chunks run side by side here: the last one is padded with
+    zeros, and adding +0.0 after the last row changes no bit.)"""
+    R, W = int(rows.shape[0]), int(rows.shape[1])
+    K = TRAJECTORIES_GRADIENT_CHUNK
+    nc = (R + K - 1) // K
+    x = rows
+    if nc * K != R:
+        x = torch.cat([rows, torch.zeros((nc * K - R, W), dtype=rows.dtype, device=rows.device)])
+    x = x.reshape(nc, K, W)
+    s = torch.zeros((nc, W), dtype=rows.dtype, device=rows.device)
+    for i in range(K):
+        s = s + x[:, i]
+    tot = torch.zeros((W,), dtype=rows.dtype, device=rows.device)
+    for c in range(nc):
+        tot = tot + s[c]
+    return tot / torch.full_like(tot, float(R))   # (a tensor divisor: a true division, not a product by 1 / R)
+
+
+def trajectories_mse_gradient(f, u0: torch.Tensor, tspan, p: torch.Tensor, saveat, target: torch.Tensor,
+                              opt: Tsit5Options | None = None, rows: bool = False, native: bool = True):
+    """(loss, dp, info) for loss = mse_loss(u, target) over the trajectories from every row of u0 [R, N], every
+    trajectory an ODE of its own with its own forward and adjoint step control (solve_trajectories' reading of a
+    matrix u0; Trainer.loss_and_grad at the matrix u0 is the other one: ONE ODE, one step size for all).  target is
+    [len(saveat), R, N], as solve_trajectories lays u out; loss is a float, dp = dloss/dp [P], the mean of the R
+    batch-1 gradients, both combined in an order that depends on R alone (combine_trajectory_rows).
+
+    "device": where solve() would run in libkanode and the handle covers the shape
+    (KanodeHandle.trajectories_gradient_supported: fp64 small chains), all solves, losses and adjoints of up to 65536
+    trajectories are ONE launch, a workgroup each, plus two small reduction launches.  "host" (uncovered handles,
+    fp32, native=False): a loop of native_mse_gradient at batch 1 where solve() is native, else autograd through
+    solve(), the rows combined in torch in the same order.
+
+    info: "path", "stop" (R names of _lib.TRAIN_STOP), "fwd_stats" and "adj_stats" (R dicts) and, with rows,
+    "dp_rows" [R, P] and "loss_rows" [R].  A trajectory that stops (maxiters, dense capacity) does not raise: stop[r]
+    names it, and loss and dp are NaN."""
+    from . import _lib as L
+    from .ode import _saveat_list, native_ok, solve
+    opt = opt or Tsit5Options()
+    if not isinstance(u0, torch.Tensor) or u0.dim() != 2 or u0.shape[0] < 1:
+        raise ValueError("trajectories_mse_gradient: u0 must be a tensor of shape [R, N]")
+    t0, tf = float(tspan[0]), float(tspan[1])
+    sv = _saveat_list(tspan, saveat)
+    u0 = u0.detach()
+    p = p.detach()
+    target = target.detach()
+    R, N = int(u0.shape[0]), int(u0.shape[1])
+    is_native = native and native_ok(f, u0, tspan, p, sv, opt)
+    if is_native:
+        tol = 1e-12 * max(1.0, abs(tf))
+        sv = [s for s in sv if s <= tf + tol]
+    if tuple(target.shape) != (len(sv), R, N):
+        raise ValueError(f"trajectories_mse_gradient: target has shape {tuple(target.shape)}, expected "
+                         f"{(len(sv), R, N)}")
+    if (is_native and len(sv) >= 1 and p.dtype == torch.float64 and opt.control == "auto"
+            and opt.replay_dts is None and opt.replay_adjoint_dts is None
+            and f.hd.trajectories_gradient_supported()):
+        pc, u0c, tc, oc = p.contiguous(), u0.contiguous(), target.contiguous(), opt.to_c()
+        if R <= TRAJECTORIES_GRADIENT_MAX:
+            loss, dp, info = f.hd.trajectories_gradient_tsit5(pc, u0c, t0, tf, sv, tc, oc, rows=rows)
+        else:   # one call per 65536 trajectories, their rows combined here in the same order
+            parts = []
+            info = {"fwd_stats": [], "adj_stats": [], "stop": []}
+            for a in range(0, R, TRAJECTORIES_GRADIENT_MAX):
+                b = min(R, a + TRAJECTORIES_GRADIENT_MAX)
+                _, _, inf = f.hd.trajectories_gradient_tsit5(pc, u0c[a:b], t0, tf, sv, tc[:, a:b].contiguous(), oc,
+                                                             rows=True)
+                parts.append(torch.cat([inf["dp_rows"], inf["loss_rows"][:, None]], dim=1))
+                for k in ("fwd_stats", "adj_stats", "stop"):
+                    info[k] += inf[k]
+            allrows = torch.cat(parts)
+            tot = combine_trajectory_rows(allrows)
+            loss, dp = float(tot[-1]), tot[:-1].contiguous()
+            if rows:
+                info["dp_rows"], info["loss_rows"] = allrows[:, :-1].contiguous(), allrows[:, -1].contiguous()
+        info["path"] = "device"
+        return loss, dp, info
+    P = p.numel()
+    nan = float("nan")
+    allrows = torch.full((R, P + 1), nan, dtype=p.dtype, device=p.device)
+    fst, ast, stop = [], [], []
+    for r in range(R):
+        ur, tr = u0[r:r + 1], target[:, r:r + 1].contiguous()
+        try:
+            if is_native:
+                lr, gr, sol = native_mse_gradient(f, ur, tspan, p, sv, opt, tr)
+            else:
+                pr = p.clone().requires_grad_(True)
+                sol = solve(f, ur, tspan, pr, sv, opt)
+                lr = torch.nn.functional.mse_loss(sol.u, tr)
+                (gr,) = torch.autograd.grad(lr, pr)
+        except (RuntimeError, L.KanodeError) as e:   # (the Python loop's error, the native one)
+            if "maxiters" not in str(e):
+                raise
+            fst.append({})
+            ast.append({})
+            stop.append("adjoint_maxiters" if "adjoint" in str(e).lower() else "forward_maxiters")
+            continue
+        allrows[r, :P] = gr.detach().reshape(-1)
+        allrows[r, P] = lr.detach()
+        st = dict(sol.stats)
+        ast.append(st.pop("adjoint", {}))
+        fst.append(st)
+        stop.append("ok")
+    tot = combine_trajectory_rows(allrows)
+    info = {"path": "host", "stop": stop, "fwd_stats": fst, "adj_stats": ast}
+    if rows:
+        info["dp_rows"], info["loss_rows"] = allrows[:, :P].contiguous(), allrows[:, P].contiguous()
+    return float(tot[-1]), tot[:-1].contiguous(), info

@@ -392,6 +392,66 @@ class KanodeHandle:
         stats = [dict(naccept=st[r].naccept, nreject=st[r].nreject, nf=st[r].nf) for r in range(R)]
         return u_save, stats, [L.SOLVE_STOP.get(int(stop[r]), str(stop[r])) for r in range(R)]
 
+    def trajectories_gradient_supported(self) -> bool:
+        """kanode_trajectories_gradient_supported: the trajectory-ensemble gradient covers this handle (an fp64 chain
+        of the one-workgroup solve at batch 1 whose column-group adjoint fits one workgroup; fused_solve on)."""
+        return bool(L.lib().kanode_trajectories_gradient_supported(self._h))
+
+    def trajectories_gradient_group(self, t0: float, tf: float, n_save: int, opts: "L.SolverOptsC") -> int:
+        """kanode_trajectories_gradient_group: the trajectories trajectories_gradient_tsit5 puts into one launch for
+        this problem (its buffer is capped at 256 MiB); more run as consecutive launch groups behind one call.
+        0: not covered."""
+        return int(L.lib().kanode_trajectories_gradient_group(self._h, float(t0), float(tf), int(n_save),
+                                                              C.byref(opts)))
+
+    def trajectories_gradient_tsit5(self, p: torch.Tensor, u0: torch.Tensor, t0: float, tf: float, saveat,
+                                    target: torch.Tensor, opts: "L.SolverOptsC", rows: bool = False,
+                                    du0: bool = False, u_save: bool = False):
+        """mse_loss over the trajectories from every row of u0 [R, N] against target [len(saveat), R, N] and its
+        gradient, every trajectory an ODE of its own with its own forward and adjoint step control, one workgroup each
+        (kanode_trajectories_gradient_tsit5).  Returns (loss (float), dp [P], info): info holds "fwd_stats" and
+        "adj_stats" (R dicts each), "stop" (R names of _lib.TRAIN_STOP) and, when asked, "dp_rows" [R, P] and
+        "loss_rows" [R] (rows), "du0" [R, N], "u_save" [len(saveat), R, N] (pre-filled with NaN).  A trajectory that
+        stops does not raise: stop[r] names the reason, its rows are NaN and so are loss and dp.  An unsupported handle
+        or a bad argument raises KanodeError."""
+        self._check_t(p, (self.P,), "p")
+        if u0.dim() != 2:
+            raise ValueError("trajectories_gradient_tsit5 needs u0 of shape [R, N]")
+        R = int(u0.shape[0])
+        self._check_t(u0, (R, self.N), "u0")
+        self._check_t(target, (len(saveat), R, self.N), "target")
+        if self.N_out != self.N:
+            raise ValueError("solve needs an RHS with N_in == N_out")
+        sv = self._saveat_c(saveat)
+
+        def new(*shape, fill=None):
+            if fill is None:
+                return torch.empty(shape, dtype=self.dtype, device=self.device)
+            return torch.full(shape, fill, dtype=self.dtype, device=self.device)
+        dp = new(self.P)
+        out_rows = new(R, self.P) if rows else None
+        out_loss = new(R) if rows else None
+        out_du0 = new(R, self.N) if du0 else None
+        out_us = new(len(saveat), R, self.N, fill=float("nan")) if u_save else None
+        loss = C.c_double(float("nan"))
+        fst = (L.SolveStatsC * max(R, 1))()
+        ast = (L.SolveStatsC * max(R, 1))()
+        stop = (C.c_int32 * max(R, 1))()
+        L.check(L.lib().kanode_trajectories_gradient_tsit5(
+            self._h, _ptr(p), _ptr(u0), R, float(t0), float(tf), sv, len(saveat), _ptr(target), C.byref(opts),
+            C.byref(loss), _ptr(dp), _ptr(out_rows), _ptr(out_loss), _ptr(out_du0), _ptr(out_us), fst, ast,
+            stop, _stream(self.device)), self._h, "kanode_trajectories_gradient_tsit5")
+        info = {"fwd_stats": [dict(naccept=fst[r].naccept, nreject=fst[r].nreject, nf=fst[r].nf) for r in range(R)],
+                "adj_stats": [dict(naccept=ast[r].naccept, nreject=ast[r].nreject, nf=ast[r].nf) for r in range(R)],
+                "stop": [L.TRAIN_STOP.get(int(stop[r]), str(stop[r])) for r in range(R)]}
+        if rows:
+            info["dp_rows"], info["loss_rows"] = out_rows, out_loss
+        if du0:
+            info["du0"] = out_du0
+        if u_save:
+            info["u_save"] = out_us
+        return float(loss.value), dp, info
+
     def _saveat_c(self, saveat):
         key = tuple(saveat)
         cache = self.__dict__.setdefault("_saveat_cache", {})

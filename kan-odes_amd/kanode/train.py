@@ -646,3 +646,75 @@ class EnsembleTrainer:
                 if res["stop"][j] != "ok":
                     self._stop(r, res["stop"][j], stop)
             at += k
+
+
+class TrajectoryTrainer:
+    """Training on R initial conditions where every trajectory is an ODE of its own (SciML's EnsembleProblem over u0
+    under one loss): the ordinary way a NeuralODE is fitted to several experiments.  u0 is [R, N], target
+    [len(saveat), R, N]; the loss is mse_loss over the whole tensor and its gradient the mean of the R batch-1
+    gradients, each solve and adjoint with its own step control (adjoint.trajectories_mse_gradient: on the GPU one
+    launch for all R where the handle covers the chain).  Trainer at the same matrix u0 solves ONE ODE over all R·N
+    entries instead: one error norm, one step size, other step counts and so another gradient.
+
+    loss_and_grad() adds the L1 term of sparse_reg on the host by Trainer's formula; step() is one Adam update
+    (kanode_adam_step on the GPU) and raises KanodeError before it when any trajectory stopped, leaving p and the
+    moments as they were.  One process: a data-parallel split over trajectories is not part of this class."""
+
+    def __init__(self, rhs, u0, tspan, saveat, target, p0, eta: float = 5e-4, solver: Tsit5Options | None = None,
+                 sparse_reg: float = 0.0):
+        if not isinstance(u0, torch.Tensor) or u0.dim() != 2:
+            raise ValueError("TrajectoryTrainer: u0 must be a tensor of shape [R, N]")
+        self.rhs, self.u0, self.tspan, self.saveat, self.target = rhs, u0, tspan, saveat, target
+        self.p = p0.detach().clone()
+        self.opt = FusedAdam(eta) if self.p.is_cuda else Adam(eta)
+        self.solver = solver or Tsit5Options()
+        self.sparse_reg = sparse_reg
+        self.history = []
+        self.last_info = None   # info of the last loss_and_grad (path, stop, the step counts)
+
+    def predict(self, p=None):
+        """solve_trajectories at p (default: the current parameters)."""
+        from .ode import solve_trajectories
+        return solve_trajectories(self.rhs, self.u0, self.tspan, self.p if p is None else p, self.saveat, self.solver)
+
+    def loss_and_grad(self):
+        """(loss (0-dim tensor), gradient [P], info) at the current parameters."""
+        from .adjoint import trajectories_mse_gradient
+        loss, g, info = trajectories_mse_gradient(self.rhs, self.u0, self.tspan, self.p, self.saveat, self.target,
+                                                  self.solver)
+        self.last_info = info
+        loss = torch.as_tensor(loss, dtype=g.dtype, device=g.device)
+        if self.sparse_reg:   # (Trainer._with_l1's statements)
+            p = self.p.detach()
+            loss = loss + reg_loss(p, self.sparse_reg, 0.0)
+            g = g + self.sparse_reg * torch.sign(p).reshape(g.shape)
+        return loss, g, info
+
+    def _step(self):
+        from . import _lib as L
+        loss, g, info = self.loss_and_grad()
+        bad = [r for r, s in enumerate(info["stop"]) if s != "ok"]
+        if bad:
+            raise L.KanodeError(f"TrajectoryTrainer.step: trajectory {bad[0]} stopped ({info['stop'][bad[0]]}); "
+                                f"{len(bad)} of {len(info['stop'])} stopped, the parameters are unchanged")
+        self.opt.update(self.p, g.contiguous())
+        lv = float(loss)
+        self.history.append(lv)
+        return lv, g
+
+    def step(self) -> float:
+        return self._step()[0]
+
+    def run(self, n_iters: int, record: bool = False) -> dict:
+        """n_iters iterations; {"loss": [...]} and, with record, "grad" and "p_before" (lists of tensors)."""
+        out = {"loss": []}
+        if record:
+            out["grad"], out["p_before"] = [], []
+        for _ in range(int(n_iters)):
+            pb = self.p.detach().clone() if record else None
+            lv, g = self._step()
+            out["loss"].append(lv)
+            if record:
+                out["grad"].append(g.detach().clone())
+                out["p_before"].append(pb)
+        return out
