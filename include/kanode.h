@@ -743,7 +743,8 @@ kanode_status kanode_solve_trajectories_tsit5(kanode_handle* h, const void* p, c
  * Covered (kanode_trajectories_gradient_supported): fp64 chain handles that kanode_fit_ensemble_tsit5's kernel covers
  * at batch 1 with the column-group adjoint: layers at most 16 wide, n_in == n_out, KANODE_OPT_FUSED_SOLVE on; the
  * unpruned [2,10,2] chain included.  Not fp32, not the Fisher-KPP field, not wider chains: KANODE_ERR_UNSUPPORTED,
- * nothing launched and nothing written.  A capturing stream is refused (KANODE_ERR_CAPTURE). */
+ * nothing launched and nothing written.  A capturing stream is refused (KANODE_ERR_CAPTURE).  fp32 handles have
+ * entries of their own below (kanode_trajectories_gradient_f32_tsit5). */
 int32_t kanode_trajectories_gradient_supported(const kanode_handle* h);
 int64_t kanode_trajectories_gradient_group(const kanode_handle* h, double t0, double tf, int64_t n_save,
                                            const kanode_solver_options* opt);
@@ -753,6 +754,34 @@ kanode_status kanode_trajectories_gradient_tsit5(kanode_handle* h, const void* p
                                                  void* dp, void* dp_rows, void* loss_rows, void* du0, void* u_save,
                                                  kanode_solve_stats* fwd_stats, kanode_solve_stats* adj_stats,
                                                  int32_t* stop, void* stream);
+
+/* --- the same gradient on an fp32 handle -------------------------------------------------------------------------
+ * The three entries above, argument for argument, for fp32 chain handles: p, u0, target, dp, dp_rows, loss_rows, du0
+ * and u_save are float arrays; *loss is a host double that holds the float total, widened.  One one-wave workgroup per
+ * trajectory (kd_chain_traj_grad_f32_kernel) runs the fp32 solve and the fp32 column-group adjoint: row r is bit for
+ * bit the gradient kanode_solve_tsit5 + kanode_adjoint_tsit5 give at batch 1 on an fp32 handle with
+ * KANODE_OPT_CHAIN_WIDE = 0, with the cotangent (u - target) * (float)(2 / (n_save * N)) formed in float.  mse_r is
+ * summed in double on the device and rounded to float once.  The totals are formed in float in the same order
+ * (chunks of 64 from 0.0f with rounded adds, the chunk sums in ascending order, one rounded division by (float)n_traj).
+ * Everything else is the fp64 entry's statement: the argument checks, 1 <= n_traj <= 65536, the stops (NaN rows, NaN
+ * totals, KANODE_OK whenever the launches ran, kanode_last_error names the lowest stopped trajectory), the capacity
+ * rule, the 256 MiB buffer and its launch groups (kanode_trajectories_gradient_f32_group: a multiple of 64, 0 where
+ * not covered), one device-to-host copy and one synchronise, a capturing stream refused.  No handle option is added,
+ * the handle's L1 penalty is NOT read, and every other path of the handle is left as it was.
+ *
+ * Covered (kanode_trajectories_gradient_f32_supported): fp32 chain handles for which kanode_solve_tsit5 runs as one
+ * workgroup at batch 1 and the fp32 column-group adjoint fits one wave: layers at most 16 wide, n_in == n_out,
+ * KANODE_OPT_FUSED_SOLVE on, P even; the [2,10,2] chain included.  fp64 handles, the Fisher-KPP field, wider chains
+ * and odd P: KANODE_ERR_UNSUPPORTED, nothing launched and nothing written. */
+int32_t kanode_trajectories_gradient_f32_supported(const kanode_handle* h);
+int64_t kanode_trajectories_gradient_f32_group(const kanode_handle* h, double t0, double tf, int64_t n_save,
+                                               const kanode_solver_options* opt);
+kanode_status kanode_trajectories_gradient_f32_tsit5(kanode_handle* h, const void* p, const void* u0, int64_t n_traj,
+                                                     double t0, double tf, const double* saveat, int64_t n_save,
+                                                     const void* target, const kanode_solver_options* opt,
+                                                     double* loss, void* dp, void* dp_rows, void* loss_rows,
+                                                     void* du0, void* u_save, kanode_solve_stats* fwd_stats,
+                                                     kanode_solve_stats* adj_stats, int32_t* stop, void* stream);
 
 /* --- the data-parallel gradient all-reduce (one process per GPU) -----------------
  * For hosts without a collective of their own (Julia, C): after kanode_adjoint_tsit5 on each rank's

@@ -728,6 +728,50 @@ function trajectories_gradient(h::Handle, u0::AbstractMatrix, tspan, p::Abstract
     return loss[], dp, rows, lrows, fst, ast, stop
 end
 
+# --- the same gradient on a Float32 handle (kanode_trajectories_gradient_f32_tsit5): float arrays, the total widened
+trajectories_gradient_f32_supported(h::Handle) =
+    ccall(sym(:kanode_trajectories_gradient_f32_supported), Int32, (Ptr{Cvoid},), h.ptr) == 1
+
+"""trajectories_gradient_f32(h, u0, tspan, p, saveat, target; kw...) -> trajectories_gradient's tuple on a Float32
+handle: dp, dp_rows and loss_rows are Float32, loss is the Float32 total as a Float64.  Covered:
+trajectories_gradient_f32_supported(h) (Float32 small chains with an even parameter count).  The handle's L1 penalty is
+not read."""
+function trajectories_gradient_f32(h::Handle, u0::AbstractMatrix, tspan, p::AbstractVector, saveat::AbstractVector,
+                                   target::AbstractArray{<:Real,3}; kw...)
+    checkp(h, p)
+    checku(h, u0, h.nin, "u0")
+    h.nin == h.nout || throw(ArgumentError("an ODE RHS needs a chain with in_dims == out_dims"))
+    T = h.T
+    T == Float32 || throw(ArgumentError("trajectories_gradient_f32: Float32 handles only"))
+    R = size(u0, 2)
+    1 <= R <= 65536 || throw(ArgumentError("trajectories_gradient_f32: 1 <= R <= 65536 trajectories"))
+    ts = Vector{Float64}(saveat)
+    (issorted(ts) && !isempty(ts)) || throw(ArgumentError("saveat must be ascending and not empty"))
+    size(target) == (h.nin, R, length(ts)) ||
+        throw(DimensionMismatch("target is $(size(target)); expected $((h.nin, R, length(ts)))"))
+    trajectories_gradient_f32_supported(h) ||
+        throw(ArgumentError("trajectories_gradient_f32: not covered for this handle"))
+    opt = options(; kw...)
+    pd, ud, xd = upload(tohost(T, p)), upload(tohost(T, u0)), upload(tohost(T, target))
+    dp, rows, lrows = zeros(T, h.P), zeros(T, h.P, R), zeros(T, R)
+    dpd, rowsd, lrowsd = upload(dp), upload(rows), upload(lrows)
+    loss = Ref{Float64}(NaN)
+    fst = Vector{SolveStats}(undef, R)
+    ast = Vector{SolveStats}(undef, R)
+    stop = zeros(Int32, R)
+    st = GC.@preserve ts fst ast stop ccall(sym(:kanode_trajectories_gradient_f32_tsit5), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Float64, Float64, Ptr{Float64}, Int64, Ptr{Cvoid},
+         Ref{SolverOptions}, Ref{Float64}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+         Ptr{SolveStats}, Ptr{SolveStats}, Ptr{Int32}, Ptr{Cvoid}),
+        h.ptr, pd.ptr, ud.ptr, R, tspan[1], tspan[2], ts, length(ts), xd.ptr, opt, loss, dpd.ptr, rowsd.ptr,
+        lrowsd.ptr, C_NULL, C_NULL, fst, ast, stop, C_NULL)
+    check(h, st)
+    download!(dp, dpd)
+    download!(rows, rowsd)
+    download!(lrows, lrowsd)
+    return loss[], dp, rows, lrows, fst, ast, stop
+end
+
 # --- pruning a sparsified KAN (LV_driver_KANODE.jl:52-108): per-edge scores on the device, the keep rule and the
 # parameter slicing on the host.  Scores are Julia [O, I] matrices (the memory kanode_edge_scores writes).
 layer_length(h::Handle, i::Integer) = Int(ccall(sym(:kanode_layer_param_length), Int64, (Ptr{Cvoid}, Int32), h.ptr, i))

@@ -2,7 +2,7 @@
 // chain has the small-chain shape, which specialisation of the kernel serves it, and for the one-workgroup adjoint
 // which model runs it, on how many threads, in how much dynamic LDS and with the dense output staged or not.
 //
-// Every launcher of kan_col.hip, kan_train.hip, kan_train_wg.hip, kan_ens_solve.hip, kan_traj_solve.hip and kan_traj_grad.hip asks here, so the ensemble
+// Every launcher of kan_col.hip, kan_train.hip, kan_train_wg.hip, kan_ens_solve.hip, kan_traj_solve.hip, kan_traj_grad.hip and kan_traj_grad_f32.hip asks here, so the ensemble
 // entries accept exactly the shapes the single launchers accept and the training loops carve LDS exactly as the
 // adjoint launcher does.  LC is the layer-constants type (kan::LayerConst; a test passes its own struct with the
 // same field names).  The numbers that belong to the device classes come in through ChainLimits, which kan_col.hip
@@ -174,6 +174,56 @@ ChainAdjPlan chain_adjoint_plan(const ChainLimits& k, const LC* hlcs, int nl, in
     if (const size_t lds = chain_group_adjoint_lds(k, nl, P, B, steps, esize))
         return {kAdjChain, chain_threads(k, B), lds, 0};
     return none;
+}
+
+// ---- the fp32 trajectory gradient (kan_traj_grad_f32.hip) -----------------------------------------------------
+// The dynamic LDS of one trajectory's workgroup (one wave, `groups` = wave / dim column groups), in BYTES after the
+// layer constants: ps [P] | rows [groups][P] | μ [2][P] | kμ [7][P] | the gradient [P] (floats; rows, μ and kμ
+// contiguous, zeroed together as kd_chain_adjoint_kernel zeroes them) | ts, dts [cap] each | saveat [n_save] (doubles)
+// | (dl_lds) u_save / dl [n_save][n] (floats).  The doubles start at a multiple of 8 bytes where 4·P is one (P even)
+// and the constants' bytes are.  (constexpr: the kernel carves with the same function.)
+struct TrajGradF32Carve {
+    size_t ps, work, mu, km, gl, tsl, dtsl, sv, dl, total;
+};
+constexpr TrajGradF32Carve traj_grad_f32_carve(int64_t P, int64_t groups, int64_t cap, int64_t n_save, int64_t n,
+                                               int dl_lds) {
+    TrajGradF32Carve c{};
+    const size_t f = sizeof(float), d = sizeof(double);
+    size_t o = 0;
+    c.ps = o, o += f * (size_t)P;
+    c.work = o, o += f * (size_t)(groups * P);
+    c.mu = o, o += f * (size_t)(2 * P);
+    c.km = o, o += f * (size_t)(7 * P);
+    c.gl = o, o += f * (size_t)P;
+    c.tsl = o, o += d * (size_t)cap;
+    c.dtsl = o, o += d * (size_t)cap;
+    c.sv = o, o += d * (size_t)n_save;
+    c.dl = o, o += dl_lds ? f * (size_t)(n_save * n) : 0;
+    c.total = o;
+    return c;
+}
+// The whole dynamic LDS of a launch with a dense output of `cap` steps, within kOneWgBudget; *dl_lds: u_save / dl live
+// in it (else in the trajectory's global block).  0: not covered (layers wider than `dim`, more layers than the
+// pullback takes, n_in != n_out, odd P: chain_group_adjoint_lds asks for (4·P) % 8 == 0) or no fit.  The adjoint is
+// the column-group model on one wave: chain_adjoint_plan at B = 1 with wide = false must give kAdjChain on `wave`
+// threads.
+template <class LC>
+size_t traj_grad_f32_lds(const ChainLimits& k, const LC* hlcs, int nl, int64_t P, int64_t cap, int64_t n_save,
+                         int* dl_lds) {
+    if (dl_lds) *dl_lds = 0;
+    if (nl < 1 || n_save < 0 || cap < 1 || !chain_small_layers(k, hlcs, nl, k.vjp_layers) ||
+        !chain_params_fit(k, nl, P, sizeof(float)) || (nl * k.lc_bytes) % 8 || (P * sizeof(float)) % 8)
+        return 0;
+    const ChainAdjPlan plan = chain_adjoint_plan(k, hlcs, nl, P, 1, false, cap, sizeof(float), false);
+    if (plan.model != kAdjChain || plan.threads != k.wave) return 0;
+    const int64_t n = hlcs[0].I;
+    auto bytes = [&](int dl) {
+        return nl * k.lc_bytes + traj_grad_f32_carve(P, k.wave / k.dim, cap, n_save, n, dl).total;
+    };
+    if (bytes(0) > kOneWgBudget) return 0;
+    const int dl = bytes(1) <= kOneWgBudget ? 1 : 0;
+    if (dl_lds) *dl_lds = dl;
+    return bytes(dl);
 }
 
 }  // namespace kan

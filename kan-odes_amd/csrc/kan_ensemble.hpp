@@ -242,4 +242,42 @@ inline int64_t traj_grad_group(int64_t P, size_t block_bytes, size_t meta_bytes,
 // the chain adjoint's meta block for this saveat list, as an upper bound (ensemble_meta_bound without a test problem)
 inline size_t traj_grad_meta_bound(int64_t n_save) { return ensemble_meta_bound(n_save, 0); }
 
+// ---- the trajectory gradient in fp32 (kanode_trajectories_gradient_f32_tsit5, kan_traj_grad_f32.hip) --------------
+// The same call with float arrays: the status words, the chunk order, the index functions of u0 / target / u_save and
+// the meta block are the ones above; what is counted in elements of `esize` bytes is stated here with that size as an
+// argument (esize = sizeof(double) gives the fp64 entry's numbers).  The handle's buffer of a call:
+//     status [R][8] int64 | loss, one 8-byte slot (the float total in its first four bytes) | part [chunks(R)][P + 1]
+//     | rows [G][P + 1] | blocks [G][block stride] | meta
+// with part, rows and the blocks in `esize` elements.  A private block of the fp32 kernel holds no gathered target
+// (the kernel reads target[:, r, :] by index):
+//     dense output [cap][7][N] | k1_0 [N] | u_save / dl [n_save][N]
+constexpr size_t traj_grad_f32_block_usave(int64_t N, int64_t cap) { return traj_grad_block_usave(N, cap); }
+constexpr size_t traj_grad_f32_block_elems(int64_t N, int64_t cap, int64_t n_save) {
+    return traj_grad_block_target(N, cap, n_save);
+}
+inline TrajGradLayout traj_grad_layout_es(int64_t R, int64_t G, int64_t P, size_t block_bytes, size_t meta_bytes,
+                                          size_t esize) {
+    TrajGradLayout L;
+    const size_t row = traj_grad_row_elems(P) * esize;
+    L.off_loss = (size_t)R * kTrajGradStatusWords * sizeof(int64_t);
+    L.off_part = ensemble_round(L.off_loss + sizeof(double));
+    L.off_rows = ensemble_round(L.off_part + (size_t)traj_grad_chunks(R) * row);
+    L.off_blocks = ensemble_round(L.off_rows + (size_t)G * row);
+    L.block_stride = ensemble_round(block_bytes);
+    L.off_meta = L.off_blocks + (size_t)G * L.block_stride;
+    L.bytes = ensemble_round(L.off_meta + meta_bytes) + 64;
+    return L;
+}
+inline size_t traj_grad_bytes_per_traj_es(int64_t P, size_t block_bytes, size_t esize) {
+    return ensemble_round(block_bytes) + traj_grad_row_elems(P) * esize;
+}
+// traj_grad_group's rule at this element size: a multiple of kTrajGradChunk, at most kTrajGradMax, 0 where no chunk fits
+inline int64_t traj_grad_group_es(int64_t P, size_t block_bytes, size_t meta_bytes, size_t budget, size_t esize) {
+    const size_t fixed = traj_grad_layout_es(kTrajGradMax, 0, P, 0, meta_bytes, esize).bytes + 128;
+    if (budget <= fixed) return 0;
+    int64_t G = (int64_t)((budget - fixed) / traj_grad_bytes_per_traj_es(P, block_bytes, esize));
+    if (G > kTrajGradMax) G = kTrajGradMax;
+    return G - G % kTrajGradChunk;
+}
+
 }  // namespace kan

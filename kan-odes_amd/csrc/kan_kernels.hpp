@@ -693,6 +693,37 @@ hipError_t launch_kd_chain_traj_grad(const LayerConst* hlcs, int nl, const Layer
 // dp [P] and *loss from all chunks(R) sums, divided by R.
 hipError_t launch_traj_grad_chunks(const double* rows, int64_t R, int64_t P, double* part, hipStream_t st);
 hipError_t launch_traj_grad_total(const double* part, int64_t R, int64_t P, double* dp, double* loss, hipStream_t st);
+// The trajectory gradient in fp32 (kan_traj_grad_f32.hip; kanode_trajectories_gradient_f32_tsit5): the same launch for
+// a small fp32 chain, workgroup r (one wave) running onewg_tsit5<float> and onewg_adjoint<float> on
+// ChainModel<float, ..> once at B = 1, bit for bit kd_chain_tsit5_kernel<float> then kd_chain_adjoint_kernel<float>.
+// t: the fields TrajGradArgs::t shares (the solver options, n_save, the device saveat list, the jump groups, cap,
+// dl_lds, dl_scale = 2 / (n_save·N), B = 1, N); its double pointers p, u0 and target are not read: the float arrays
+// are the fields below.  rows, dp_rows, loss_rows, du0, u_save and the private blocks hold floats; the status words
+// are TrajGradArgs'.  The kernel reads target[:, r, :] by index (no gathered copy in the block).
+struct TrajGradF32Args {
+    ChainTrainArgs t;
+    const float* p;          // [P]
+    const float* u0;         // [R][N], at this launch's first trajectory
+    const float* target;     // [n_save][R_all][N], at this launch's first trajectory
+    float* u_save;           // as target, or null
+    int64_t R_all;
+    char* blocks;            // [R][block_stride bytes] (traj_grad_f32_block_elems floats used)
+    size_t block_stride;
+    float* rows;             // [R][P + 1]
+    float* dp_rows;          // [R][P] or null
+    float* loss_rows;        // [R] or null
+    float* du0;              // [R][N] or null
+    int64_t* status;         // [R][8]
+};
+// the shapes covered: kan_chain_plan.hpp's traj_grad_f32_lds fits at a capacity of one step
+bool chain_traj_grad_f32_supported(const LayerConst* hlcs, int nl, int64_t P);
+// the dynamic LDS of a launch (0: does not fit); *dl_lds: u_save / dl live in LDS
+size_t chain_traj_grad_f32_lds(const LayerConst* hlcs, int nl, int64_t P, int64_t cap, int64_t n_save, int* dl_lds);
+hipError_t launch_kd_chain_traj_grad_f32(const LayerConst* hlcs, int nl, const LayerConst* lcs, int64_t P,
+                                         const TrajGradF32Args& g, int64_t R, hipStream_t st);
+// launch_traj_grad_chunks / launch_traj_grad_total on float rows: the same order, __fadd_rn and one __fdiv_rn
+hipError_t launch_traj_grad_chunks_f32(const float* rows, int64_t R, int64_t P, float* part, hipStream_t st);
+hipError_t launch_traj_grad_total_f32(const float* part, int64_t R, int64_t P, float* dp, float* loss, hipStream_t st);
 
 // surrogate shapes (kan_wide.hip)
 constexpr int kWideKT = 8;       // column tile of the wide-out kernels

@@ -18,6 +18,7 @@ struct ChainSolveArgs;
 struct ChainAdjointArgs;
 struct ChainTrainArgs;
 struct TrajGradArgs;
+struct TrajGradF32Args;
 struct EnsembleReplicas;
 struct AdjStepArgs;
 struct PairAdjArgs;
@@ -219,6 +220,17 @@ int64_t kanode_internal_traj_grad_group(const kanode_handle* h, bool adaptive, d
 kanode_status kanode_internal_traj_grad(kanode_handle* h, kan::TrajGradArgs* g, int64_t R,
                                         const std::vector<char>& meta, int64_t* res, double* loss, double* dp,
                                         void* stream);
+// kanode_trajectories_gradient_f32_tsit5 (kd_chain_traj_grad_f32_kernel and the float reduction launches,
+// kan_traj_grad_f32.hip): the same three by the same statement (kanode_train_launch.cpp's traj_grad_run) on an fp32
+// chain.  _ok: fp32 chains the one-workgroup solve runs at batch 1 whose column-group adjoint fits one wave (layers
+// <= 16 wide, n_in == n_out, P even).  g's arrays, the rows, the chunk sums and dp hold floats; *loss is the float
+// total, widened.  The buffers are the handle's traj_grad_buf / traj_grad_host (a handle has one dtype).
+bool kanode_internal_traj_grad_f32_ok(const kanode_handle* h);
+int64_t kanode_internal_traj_grad_f32_group(const kanode_handle* h, bool adaptive, double t0, double tf, double dt,
+                                            int64_t n_save);
+kanode_status kanode_internal_traj_grad_f32(kanode_handle* h, kan::TrajGradF32Args* g, int64_t R,
+                                            const std::vector<char>& meta, int64_t* res, double* loss, float* dp,
+                                            void* stream);
 // the device-resident Fisher-KPP training loop on the forward-mode gradient (fk_small_train_kernel,
 // kanode_train_forward_tsit5): whether the handle takes it at this batch (with_test: with the logged-loss solve),
 // and one launch.  meta = saveat [n_save] | saveat_test [n_save_test] (doubles), kept on the handle with the two

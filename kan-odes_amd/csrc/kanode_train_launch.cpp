@@ -105,12 +105,13 @@ struct TrainWgFit {
     int dl_lds, stage_rec;
     size_t rec_bytes;   // the private global block (ChainTrainArgs::rec), a multiple of 64 bytes
 };
-// (wide: the adjoint's model is chosen with it; the trajectory gradient passes false, the loops the handle's option)
-static bool chain_train_wg_fit(const kanode_handle* h, int64_t batch, bool wide, bool adaptive, double t0, double tf,
-                               double dt, int64_t n_save, int64_t n_save_test, TrainWgFit& f) {
-    auto lds = [&](int64_t cap, int* dl, int* sr) {
-        return kan::chain_train_wg_lds(h->hlc, h->n_layers, h->P, batch, wide, cap, n_save, n_save_test, dl, sr);
-    };
+// The capacity rule of the one-workgroup loops and of both trajectory gradients: KANODE_OPT_FUSED_SOLVE_CAP where set,
+// else the largest capacity <= kChainAdjointMaxSteps that fits with u_save / dl in LDS (at least 64, else the largest
+// that fits at all); a fixed-step solve without the option takes its own step count.  lds(cap, &dl, &sr): the launch's
+// dynamic LDS at that capacity (0: no fit) and its two flags (either pointer may be null).
+template <class Lds>
+static bool onewg_cap_fit(const kanode_handle* h, bool adaptive, double t0, double tf, double dt, Lds&& lds,
+                          int64_t& cap_out, int& dl_out, int& sr_out) {
     int64_t cap = std::min<int64_t>(h->opt.fused_solve_cap, kan::kChainAdjointMaxSteps);
     if (cap < 1) {
         auto largest = [&](bool want_dl) {   // the largest cap that fits (want_dl: with u_save / dl in LDS), 0: none
@@ -126,6 +127,20 @@ static bool chain_train_wg_fit(const kanode_handle* h, int64_t batch, bool wide,
         cap = std::max<int64_t>(kanode_fixed_step_count(t0, tf, dt, kan::kChainAdjointMaxSteps), 1);
     int dl = 0, sr = 0;
     if (cap < 1 || !lds(cap, &dl, &sr)) return false;
+    cap_out = cap;
+    dl_out = dl;
+    sr_out = sr;
+    return true;
+}
+// (wide: the adjoint's model is chosen with it; the trajectory gradient passes false, the loops the handle's option)
+static bool chain_train_wg_fit(const kanode_handle* h, int64_t batch, bool wide, bool adaptive, double t0, double tf,
+                               double dt, int64_t n_save, int64_t n_save_test, TrainWgFit& f) {
+    auto lds = [&](int64_t cap, int* dl, int* sr) {
+        return kan::chain_train_wg_lds(h->hlc, h->n_layers, h->P, batch, wide, cap, n_save, n_save_test, dl, sr);
+    };
+    int64_t cap = 0;
+    int dl = 0, sr = 0;
+    if (!onewg_cap_fit(h, adaptive, t0, tf, dt, lds, cap, dl, sr)) return false;
     f.cap = cap;
     f.dl_lds = dl;
     f.stage_rec = sr;
@@ -225,43 +240,95 @@ kanode_status kanode_internal_chain_train(kanode_handle* h, int64_t batch, kan::
                         });
 }
 
-// ---- the trajectory gradient (kan_traj_grad.hip) ----
-bool kanode_internal_traj_grad_ok(const kanode_handle* h) {
-    return h->spec.dtype == KANODE_F64 && h->spec.rhs_kind == KANODE_RHS_CHAIN && h->n_in == h->n_out &&
-           kanode_internal_chain_tsit5_ok(h, 1) &&
-           kan::chain_traj_grad_supported(h->hlc, h->n_layers, h->P, h->esize);
-}
-// the capacity by kanode_fit_ensemble_tsit5's rules at batch 1 on the ChainModel adjoint, and a trajectory's block
+// ---- the trajectory gradient (kan_traj_grad.hip, kan_traj_grad_f32.hip) ----
+// One statement for both element types.  TrajGradKind<T>: the argument struct, whether the handle is covered, the
+// capacity and a trajectory's block, and the three launches.
+template <typename T>
+struct TrajGradKind;
+template <>
+struct TrajGradKind<double> {
+    using Args = kan::TrajGradArgs;
+    static const char* name() { return "kanode_trajectories_gradient_tsit5"; }
+    static bool ok(const kanode_handle* h) {
+        return h->spec.dtype == KANODE_F64 && h->spec.rhs_kind == KANODE_RHS_CHAIN && h->n_in == h->n_out &&
+               kanode_internal_chain_tsit5_ok(h, 1) &&
+               kan::chain_traj_grad_supported(h->hlc, h->n_layers, h->P, h->esize);
+    }
+    // the capacity by kanode_fit_ensemble_tsit5's rules at batch 1 on the ChainModel adjoint, and a trajectory's block
+    static bool fit(const kanode_handle* h, bool adaptive, double t0, double tf, double dt, int64_t n_save,
+                    TrainWgFit& f, size_t& block_bytes) {
+        if (!chain_train_wg_fit(h, 1, false, adaptive, t0, tf, dt, n_save, 0, f) || f.stage_rec) return false;
+        block_bytes = sizeof(double) * kan::traj_grad_block_elems(h->n_in, f.cap, n_save);
+        return true;
+    }
+    static hipError_t launch(const kanode_handle* h, const Args& g, int64_t R, hipStream_t st) {
+        return kan::launch_kd_chain_traj_grad(h->hlc, h->n_layers, h->dlc(), h->P, g, R, st);
+    }
+    static hipError_t chunks(const double* rows, int64_t R, int64_t P, double* part, hipStream_t st) {
+        return kan::launch_traj_grad_chunks(rows, R, P, part, st);
+    }
+    static hipError_t total(const double* part, int64_t R, int64_t P, double* dp, double* loss, hipStream_t st) {
+        return kan::launch_traj_grad_total(part, R, P, dp, loss, st);
+    }
+};
+template <>
+struct TrajGradKind<float> {
+    using Args = kan::TrajGradF32Args;
+    static const char* name() { return "kanode_trajectories_gradient_f32_tsit5"; }
+    static bool ok(const kanode_handle* h) {
+        return h->spec.dtype == KANODE_F32 && h->spec.rhs_kind == KANODE_RHS_CHAIN && h->n_in == h->n_out &&
+               kanode_internal_chain_tsit5_ok(h, 1) && kan::chain_traj_grad_f32_supported(h->hlc, h->n_layers, h->P);
+    }
+    // the same capacity rule on kan_chain_plan.hpp's traj_grad_f32_lds; the block holds no gathered target
+    static bool fit(const kanode_handle* h, bool adaptive, double t0, double tf, double dt, int64_t n_save,
+                    TrainWgFit& f, size_t& block_bytes) {
+        auto lds = [&](int64_t cap, int* dl, int* sr) {
+            if (sr) *sr = 0;
+            return kan::chain_traj_grad_f32_lds(h->hlc, h->n_layers, h->P, cap, n_save, dl);
+        };
+        if (!onewg_cap_fit(h, adaptive, t0, tf, dt, lds, f.cap, f.dl_lds, f.stage_rec)) return false;
+        block_bytes = sizeof(float) * kan::traj_grad_f32_block_elems(h->n_in, f.cap, n_save);
+        return true;
+    }
+    static hipError_t launch(const kanode_handle* h, const Args& g, int64_t R, hipStream_t st) {
+        return kan::launch_kd_chain_traj_grad_f32(h->hlc, h->n_layers, h->dlc(), h->P, g, R, st);
+    }
+    static hipError_t chunks(const float* rows, int64_t R, int64_t P, float* part, hipStream_t st) {
+        return kan::launch_traj_grad_chunks_f32(rows, R, P, part, st);
+    }
+    static hipError_t total(const float* part, int64_t R, int64_t P, float* dp, float* loss, hipStream_t st) {
+        return kan::launch_traj_grad_total_f32(part, R, P, dp, loss, st);
+    }
+};
+template <typename T>
 static bool traj_grad_fit(const kanode_handle* h, bool adaptive, double t0, double tf, double dt, int64_t n_save,
                           TrainWgFit& f, size_t& block_bytes) {
-    if (n_save < 1 || !(tf > t0) || !kanode_internal_traj_grad_ok(h) ||
-        !chain_train_wg_fit(h, 1, false, adaptive, t0, tf, dt, n_save, 0, f) || f.stage_rec)
-        return false;
-    block_bytes = sizeof(double) * kan::traj_grad_block_elems(h->n_in, f.cap, n_save);
-    return true;
+    return n_save >= 1 && tf > t0 && TrajGradKind<T>::ok(h) &&
+           TrajGradKind<T>::fit(h, adaptive, t0, tf, dt, n_save, f, block_bytes);
 }
-int64_t kanode_internal_traj_grad_group(const kanode_handle* h, bool adaptive, double t0, double tf, double dt,
-                                        int64_t n_save) {
+template <typename T>
+static int64_t traj_grad_group(const kanode_handle* h, bool adaptive, double t0, double tf, double dt, int64_t n_save) {
     TrainWgFit f{};
     size_t block_bytes = 0;
-    if (!traj_grad_fit(h, adaptive, t0, tf, dt, n_save, f, block_bytes)) return 0;
-    return kan::traj_grad_group(h->P, block_bytes, kan::traj_grad_meta_bound(n_save), kan::kEnsembleBudget);
+    if (!traj_grad_fit<T>(h, adaptive, t0, tf, dt, n_save, f, block_bytes)) return 0;
+    return kan::traj_grad_group_es(h->P, block_bytes, kan::traj_grad_meta_bound(n_save), kan::kEnsembleBudget, sizeof(T));
 }
-kanode_status kanode_internal_traj_grad(kanode_handle* h, kan::TrajGradArgs* g, int64_t R,
-                                        const std::vector<char>& meta, int64_t* res, double* loss, double* dp,
-                                        void* stream) {
-    const hipStream_t st = (hipStream_t)stream;
-    const std::string what = "kanode_trajectories_gradient_tsit5";
+template <typename T>
+static kanode_status traj_grad_run(kanode_handle* h, typename TrajGradKind<T>::Args* g, int64_t R,
+                                   const std::vector<char>& meta, int64_t* res, double* loss, T* dp, hipStream_t st) {
+    using K = TrajGradKind<T>;
+    const std::string what = K::name();
     kan::ChainTrainArgs& a = g->t;
     TrainWgFit f{};
     size_t block_bytes = 0;
-    if (!traj_grad_fit(h, a.adaptive != 0, a.t0, a.tf, a.dt, a.n_save, f, block_bytes))
+    if (!traj_grad_fit<T>(h, a.adaptive != 0, a.t0, a.tf, a.dt, a.n_save, f, block_bytes))
         return fail(h, KANODE_ERR_UNSUPPORTED, what + ": not supported (the problem does not fit one workgroup's LDS)");
-    const int64_t G = kan::traj_grad_group(h->P, block_bytes, kan::traj_grad_meta_bound(a.n_save), kan::kEnsembleBudget);
-    if (G < 1 || meta.size() > kan::traj_grad_meta_bound(a.n_save))
+    const size_t meta_bound = kan::traj_grad_meta_bound(a.n_save);
+    const int64_t G = kan::traj_grad_group_es(h->P, block_bytes, meta_bound, kan::kEnsembleBudget, sizeof(T));
+    if (G < 1 || meta.size() > meta_bound)
         return fail(h, KANODE_ERR_UNSUPPORTED, what + ": not supported (a launch group does not fit the handle's buffer)");
     const int64_t Gn = std::min(R, G);
-    const kan::TrajGradLayout L = kan::traj_grad_layout(R, Gn, h->P, block_bytes, meta.size());
+    const kan::TrajGradLayout L = kan::traj_grad_layout_es(R, Gn, h->P, block_bytes, meta.size(), sizeof(T));
     const size_t host_bytes = kan::traj_grad_host_bytes(R);
     if (h->traj_grad_buf.bytes() < L.bytes || h->traj_grad_host.bytes() < host_bytes) {
         HIP_TRY(h, hipStreamSynchronize(st));   // (an earlier call's kernels may still use the old buffers)
@@ -282,43 +349,65 @@ kanode_status kanode_internal_traj_grad(kanode_handle* h, kan::TrajGradArgs* g, 
     a.stage_rec = 0;
     a.B = 1;
     a.N = h->n_in;
-    const kan::TrajGradArgs all = *g;
+    const typename K::Args all = *g;
     const size_t N = (size_t)h->n_in, P = (size_t)h->P;
-    double* const part = (double*)(base + L.off_part);
-    double* const dloss = (double*)(base + L.off_loss);
+    T* const part = (T*)(base + L.off_part);
+    T* const dloss = (T*)(base + L.off_loss);
     // consecutive groups of G trajectories, one launch and its chunk sums each, in stream order (they share the
     // rows and the blocks); G is a multiple of the chunk, so a group's chunks are whole
     for (int64_t g0 = 0; g0 < R; g0 += G) {
         const int64_t Rg = std::min(G, R - g0);
-        kan::TrajGradArgs gg = all;
+        typename K::Args gg = all;
         gg.u0 = all.u0 + (size_t)g0 * N;
         gg.target = all.target + (size_t)g0 * N;
         gg.u_save = all.u_save ? all.u_save + (size_t)g0 * N : nullptr;
         gg.R_all = R;
         gg.blocks = base + L.off_blocks;
         gg.block_stride = L.block_stride;
-        gg.rows = (double*)(base + L.off_rows);
+        gg.rows = (T*)(base + L.off_rows);
         gg.dp_rows = all.dp_rows ? all.dp_rows + (size_t)g0 * P : nullptr;
         gg.loss_rows = all.loss_rows ? all.loss_rows + g0 : nullptr;
         gg.du0 = all.du0 ? all.du0 + (size_t)g0 * N : nullptr;
         gg.status = (int64_t*)base + kan::traj_grad_status_word(g0);
-        hipError_t e = kan::launch_kd_chain_traj_grad(h->hlc, h->n_layers, h->dlc(), h->P, gg, Rg, st);
+        hipError_t e = K::launch(h, gg, Rg, st);
         if (e == hipErrorNotSupported)
             return fail(h, KANODE_ERR_UNSUPPORTED, what + ": not supported (shape or saveat list not covered by the "
                                                           "one-workgroup kernel)");
         if (e == hipSuccess)
-            e = kan::launch_traj_grad_chunks(gg.rows, Rg, h->P,
-                                             part + (size_t)(g0 / kan::kTrajGradChunk) * kan::traj_grad_row_elems(h->P), st);
+            e = K::chunks(gg.rows, Rg, h->P,
+                          part + (size_t)(g0 / kan::kTrajGradChunk) * kan::traj_grad_row_elems(h->P), st);
         if (e != hipSuccess) return fail(h, KANODE_ERR_HIP, what + " launch: " + hipGetErrorString(e));
     }
-    if (const hipError_t e = kan::launch_traj_grad_total(part, R, h->P, dp, dloss, st); e != hipSuccess)
+    if (const hipError_t e = K::total(part, R, h->P, dp, dloss, st); e != hipSuccess)
         return fail(h, KANODE_ERR_HIP, what + " reduction: " + hipGetErrorString(e));
     HIP_TRY(h, hipMemcpyAsync(h->traj_grad_host.ptr(), base, host_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     const char* hp = h->traj_grad_host.as<char>();
     std::memcpy(res, hp, (size_t)R * kan::kTrajGradStatusWords * sizeof(int64_t));
-    std::memcpy(loss, hp + L.off_loss, sizeof(double));
+    T total = T(0);
+    std::memcpy(&total, hp + L.off_loss, sizeof(T));
+    *loss = (double)total;
     return KANODE_OK;
+}
+bool kanode_internal_traj_grad_ok(const kanode_handle* h) { return TrajGradKind<double>::ok(h); }
+int64_t kanode_internal_traj_grad_group(const kanode_handle* h, bool adaptive, double t0, double tf, double dt,
+                                        int64_t n_save) {
+    return traj_grad_group<double>(h, adaptive, t0, tf, dt, n_save);
+}
+kanode_status kanode_internal_traj_grad(kanode_handle* h, kan::TrajGradArgs* g, int64_t R,
+                                        const std::vector<char>& meta, int64_t* res, double* loss, double* dp,
+                                        void* stream) {
+    return traj_grad_run<double>(h, g, R, meta, res, loss, dp, (hipStream_t)stream);
+}
+bool kanode_internal_traj_grad_f32_ok(const kanode_handle* h) { return TrajGradKind<float>::ok(h); }
+int64_t kanode_internal_traj_grad_f32_group(const kanode_handle* h, bool adaptive, double t0, double tf, double dt,
+                                            int64_t n_save) {
+    return traj_grad_group<float>(h, adaptive, t0, tf, dt, n_save);
+}
+kanode_status kanode_internal_traj_grad_f32(kanode_handle* h, kan::TrajGradF32Args* g, int64_t R,
+                                            const std::vector<char>& meta, int64_t* res, double* loss, float* dp,
+                                            void* stream) {
+    return traj_grad_run<float>(h, g, R, meta, res, loss, dp, (hipStream_t)stream);
 }
 
 bool kanode_internal_fk_train_ok(const kanode_handle* h, int64_t batch, bool with_test) {

@@ -1,4 +1,5 @@
-// kanode_traj_grad.cpp — kanode_trajectories_gradient_tsit5 (include/kanode.h): the loss mean((u - target)²) over
+// kanode_traj_grad.cpp — kanode_trajectories_gradient_tsit5 and its fp32 twin kanode_trajectories_gradient_f32_tsit5
+// (include/kanode.h), one statement for both (trajectories_gradient<K>): the loss mean((u - target)²) over
 // n_traj trajectories of one problem at one parameter vector and its gradient, every trajectory an ODE of its own
 // with its own forward and adjoint step control, one workgroup each (kan_traj_grad.hip), the rows combined in a fixed
 // order.  The argument checks are kanode_solve_tsit5's statements, the jump groups kanode_adjoint_tsit5's; the stop
@@ -6,24 +7,52 @@
 #include "kan_ensemble.hpp"
 #include "kanode_solve_internal.hpp"
 
-extern "C" int32_t kanode_trajectories_gradient_supported(const kanode_handle* h) {
-    return h && kanode_internal_traj_grad_ok(h) ? 1 : 0;
-}
+namespace {
 
-extern "C" int64_t kanode_trajectories_gradient_group(const kanode_handle* h, double t0, double tf, int64_t n_save,
-                                                      const kanode_solver_options* opt) {
-    if (!h) return 0;
-    const kanode_solver_options o = resolved(opt);
-    return kanode_internal_traj_grad_group(h, o.adaptive != 0, t0, tf, o.dt, n_save);
-}
+// what differs between the fp64 entry and the fp32 one: the argument struct, the element type and the three calls of
+// kanode_train_launch.cpp
+struct GradF64 {
+    using Args = kan::TrajGradArgs;
+    using T = double;
+    static const char* name() { return "kanode_trajectories_gradient_tsit5"; }
+    static const char* covered() {
+        return ": not supported (covered: fp64 chains for which the one-workgroup solve of kanode_solve_tsit5 runs at "
+               "batch 1 and the column-group adjoint fits: layers <= 16 wide, n_in == n_out, fused_solve on; not fp32, "
+               "not the Fisher-KPP field)";
+    }
+    static bool ok(const kanode_handle* h) { return kanode_internal_traj_grad_ok(h); }
+    static void set_p(Args& g, const void* p) { g.t.p = (double*)p; }   // (read only)
+    static kanode_status run(kanode_handle* h, Args* g, int64_t R, const std::vector<char>& meta, int64_t* res,
+                             double* loss, void* dp, void* st) {
+        return kanode_internal_traj_grad(h, g, R, meta, res, loss, (double*)dp, st);
+    }
+};
+struct GradF32 {
+    using Args = kan::TrajGradF32Args;
+    using T = float;
+    static const char* name() { return "kanode_trajectories_gradient_f32_tsit5"; }
+    static const char* covered() {
+        return ": not supported (covered: fp32 chains for which the one-workgroup solve of kanode_solve_tsit5 runs at "
+               "batch 1 and the fp32 column-group adjoint fits: layers <= 16 wide, n_in == n_out, fused_solve on, P "
+               "even; not fp64, not the Fisher-KPP field)";
+    }
+    static bool ok(const kanode_handle* h) { return kanode_internal_traj_grad_f32_ok(h); }
+    static void set_p(Args& g, const void* p) { g.p = (const float*)p; }
+    static kanode_status run(kanode_handle* h, Args* g, int64_t R, const std::vector<char>& meta, int64_t* res,
+                             double* loss, void* dp, void* st) {
+        return kanode_internal_traj_grad_f32(h, g, R, meta, res, loss, (float*)dp, st);
+    }
+};
 
-extern "C" kanode_status kanode_trajectories_gradient_tsit5(
+template <class K>
+kanode_status trajectories_gradient(
     kanode_handle* h, const void* p, const void* u0, int64_t n_traj, double t0, double tf, const double* saveat,
     int64_t n_save, const void* target, const kanode_solver_options* opt, double* loss, void* dp, void* dp_rows,
     void* loss_rows, void* du0, void* u_save, kanode_solve_stats* fwd_stats, kanode_solve_stats* adj_stats,
     int32_t* stop, void* stream) {
+    using T = typename K::T;
     SOLVE_TRY(kanode_internal_check(h));
-    const std::string name = "kanode_trajectories_gradient_tsit5";
+    const std::string name = K::name();
     if (n_traj < 1 || n_traj > kan::kTrajGradMax)
         return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": 1 <= n_traj <= 65536");
     kanode_solver_options o = resolved(opt);
@@ -35,11 +64,7 @@ extern "C" kanode_status kanode_trajectories_gradient_tsit5(
     SOLVE_TRY(check_saveat(h, saveat, n_save, tf));
     if (check_saveat(saveat, n_save, tf, &t0) != kSaveatOk)
         return kanode_internal_fail(h, KANODE_ERR_INVALID_ARG, name + ": saveat must ascend within [t0, tf]");
-    if (!kanode_internal_traj_grad_ok(h))
-        return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED,
-                                    name + ": not supported (covered: fp64 chains for which the one-workgroup solve of "
-                                    "kanode_solve_tsit5 runs at batch 1 and the column-group adjoint fits: layers <= "
-                                    "16 wide, n_in == n_out, fused_solve on; not fp32, not the Fisher-KPP field)");
+    if (!K::ok(h)) return kanode_internal_fail(h, KANODE_ERR_UNSUPPORTED, name + K::covered());
     hipStream_t st = (hipStream_t)stream;
     if (capturing(st)) return kanode_internal_fail(h, KANODE_ERR_CAPTURE, name + " reads its status words");
     // the adjoint's stops and jump groups (those of kanode_adjoint_tsit5 for this saveat), one copy for all
@@ -59,23 +84,23 @@ extern "C" kanode_status kanode_trajectories_gradient_tsit5(
         put(off.data(), off.size() * sizeof(int32_t));
         put(rows.data(), rows.size() * sizeof(int32_t));
     }
-    kan::TrajGradArgs g{};
+    typename K::Args g{};
     set_span_opts(g.t, t0, tf, o);
-    g.t.p = (double*)p;   // (read only)
+    K::set_p(g, p);
     g.t.n_save = n_save;
     g.t.dl_scale = 2.0 / (double)(n_save * kanode_internal_state_length(h));   // each trajectory's own MSE
     g.t.nstops = ns;
     g.t.n_iters = 1;
-    g.u0 = (const double*)u0;
-    g.target = (const double*)target;
-    g.u_save = (double*)u_save;
+    g.u0 = (const T*)u0;
+    g.target = (const T*)target;
+    g.u_save = (T*)u_save;
     g.R_all = n_traj;
-    g.dp_rows = (double*)dp_rows;
-    g.loss_rows = (double*)loss_rows;
-    g.du0 = (double*)du0;
+    g.dp_rows = (T*)dp_rows;
+    g.loss_rows = (T*)loss_rows;
+    g.du0 = (T*)du0;
     std::vector<int64_t> res((size_t)n_traj * kan::kTrajGradStatusWords, 0);
     double total = 0.0;
-    SOLVE_TRY(kanode_internal_traj_grad(h, &g, n_traj, meta, res.data(), &total, (double*)dp, st));
+    SOLVE_TRY(K::run(h, &g, n_traj, meta, res.data(), &total, dp, st));
     *loss = total;
     static const char* const why[] = {"", "forward Tsit5: maxiters reached", "forward dense-output capacity exceeded "
                                       "(KANODE_OPT_FUSED_SOLVE_CAP)", "adjoint Tsit5: maxiters reached",
@@ -97,4 +122,46 @@ extern "C" kanode_status kanode_trajectories_gradient_tsit5(
         (void)kanode_internal_fail(h, KANODE_ERR_INVALID_ARG,
                                    name + ": trajectory " + std::to_string(bad) + ": " + why[stop[bad]]);
     return KANODE_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t kanode_trajectories_gradient_supported(const kanode_handle* h) {
+    return h && kanode_internal_traj_grad_ok(h) ? 1 : 0;
+}
+
+extern "C" int64_t kanode_trajectories_gradient_group(const kanode_handle* h, double t0, double tf, int64_t n_save,
+                                                      const kanode_solver_options* opt) {
+    if (!h) return 0;
+    const kanode_solver_options o = resolved(opt);
+    return kanode_internal_traj_grad_group(h, o.adaptive != 0, t0, tf, o.dt, n_save);
+}
+
+extern "C" kanode_status kanode_trajectories_gradient_tsit5(
+    kanode_handle* h, const void* p, const void* u0, int64_t n_traj, double t0, double tf, const double* saveat,
+    int64_t n_save, const void* target, const kanode_solver_options* opt, double* loss, void* dp, void* dp_rows,
+    void* loss_rows, void* du0, void* u_save, kanode_solve_stats* fwd_stats, kanode_solve_stats* adj_stats,
+    int32_t* stop, void* stream) {
+    return trajectories_gradient<GradF64>(h, p, u0, n_traj, t0, tf, saveat, n_save, target, opt, loss, dp, dp_rows,
+                                          loss_rows, du0, u_save, fwd_stats, adj_stats, stop, stream);
+}
+
+extern "C" int32_t kanode_trajectories_gradient_f32_supported(const kanode_handle* h) {
+    return h && kanode_internal_traj_grad_f32_ok(h) ? 1 : 0;
+}
+
+extern "C" int64_t kanode_trajectories_gradient_f32_group(const kanode_handle* h, double t0, double tf, int64_t n_save,
+                                                          const kanode_solver_options* opt) {
+    if (!h) return 0;
+    const kanode_solver_options o = resolved(opt);
+    return kanode_internal_traj_grad_f32_group(h, o.adaptive != 0, t0, tf, o.dt, n_save);
+}
+
+extern "C" kanode_status kanode_trajectories_gradient_f32_tsit5(
+    kanode_handle* h, const void* p, const void* u0, int64_t n_traj, double t0, double tf, const double* saveat,
+    int64_t n_save, const void* target, const kanode_solver_options* opt, double* loss, void* dp, void* dp_rows,
+    void* loss_rows, void* du0, void* u_save, kanode_solve_stats* fwd_stats, kanode_solve_stats* adj_stats,
+    int32_t* stop, void* stream) {
+    return trajectories_gradient<GradF32>(h, p, u0, n_traj, t0, tf, saveat, n_save, target, opt, loss, dp, dp_rows,
+                                          loss_rows, du0, u_save, fwd_stats, adj_stats, stop, stream);
 }

@@ -164,6 +164,14 @@ SIGNATURES = [
                                                      C.POINTER(C.c_double), _P, _P, _P, _P, _P,
                                                      C.POINTER(SolveStatsC), C.POINTER(SolveStatsC),
                                                      C.POINTER(C.c_int32), _P]),
+    ("kanode_trajectories_gradient_f32_supported", C.c_int32, [_H]),
+    ("kanode_trajectories_gradient_f32_group", C.c_int64, [_H, C.c_double, C.c_double, C.c_int64,
+                                                           C.POINTER(SolverOptsC)]),
+    ("kanode_trajectories_gradient_f32_tsit5", C.c_int, [_H, _P, _P, C.c_int64, C.c_double, C.c_double,
+                                                         C.POINTER(C.c_double), C.c_int64, _P,
+                                                         C.POINTER(SolverOptsC), C.POINTER(C.c_double), _P, _P, _P, _P,
+                                                         _P, C.POINTER(SolveStatsC), C.POINTER(SolveStatsC),
+                                                         C.POINTER(C.c_int32), _P]),
     ("kanode_adjoint_tsit5", C.c_int, [_H, _P, _P, _P, _P, _P, C.POINTER(SolverOptsC), C.POINTER(SolveStatsC), _P]),
     ("kanode_adjoint_step_sizes", C.c_int64, [_H, _P, C.c_int64]),
     ("kanode_table_rejections", C.c_int, [_H, _P]),

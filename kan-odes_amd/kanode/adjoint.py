@@ -382,7 +382,8 @@ def combine_trajectory_rows(rows: torch.Tensor) -> torch.Tensor:
 
 
 def trajectories_mse_gradient(f, u0: torch.Tensor, tspan, p: torch.Tensor, saveat, target: torch.Tensor,
-                              opt: Tsit5Options | None = None, rows: bool = False, native: bool = True):
+                              opt: Tsit5Options | None = None, rows: bool = False, native: bool = True,
+                              f32: str = "host"):
     """(loss, dp, info) for loss = mse_loss(u, target) over the trajectories from every row of u0 [R, N], every
     trajectory an ODE of its own with its own forward and adjoint step control (solve_trajectories' reading of a
     matrix u0; Trainer.loss_and_grad at the matrix u0 is the other one: ONE ODE, one step size for all).  target is
@@ -394,6 +395,12 @@ def trajectories_mse_gradient(f, u0: torch.Tensor, tspan, p: torch.Tensor, savea
     trajectories are ONE launch, a workgroup each, plus two small reduction launches.  "host" (uncovered handles,
     fp32, native=False): a loop of native_mse_gradient at batch 1 where solve() is native, else autograd through
     solve(), the rows combined in torch in the same order.
+
+    f32: what a float32 p does.  "host" (the default; a later change may flip it): the host loop, as before.
+    "device": the fp32 entry (KanodeHandle.trajectories_gradient_f32_supported: fp32 small chains with an even
+    parameter count), one launch per 65536 trajectories as above, info["path"] == "device"; elsewhere the host loop.
+    Its gradient rows are bitwise the host loop's on a handle with chain_wide = 0; its per-trajectory losses are summed
+    in double and rounded once, where the host loop's are torch's float mse_loss.
 
     info: "path", "stop" (R names of _lib.TRAIN_STOP), "fwd_stats" and "adj_stats" (R dicts) and, with rows,
     "dp_rows" [R, P] and "loss_rows" [R].  A trajectory that stops (maxiters, dense capacity) does not raise: stop[r]
@@ -416,19 +423,25 @@ def trajectories_mse_gradient(f, u0: torch.Tensor, tspan, p: torch.Tensor, savea
     if tuple(target.shape) != (len(sv), R, N):
         raise ValueError(f"trajectories_mse_gradient: target has shape {tuple(target.shape)}, expected "
                          f"{(len(sv), R, N)}")
-    if (is_native and len(sv) >= 1 and p.dtype == torch.float64 and opt.control == "auto"
-            and opt.replay_dts is None and opt.replay_adjoint_dts is None
-            and f.hd.trajectories_gradient_supported()):
+    if f32 not in ("host", "device"):
+        raise ValueError("trajectories_mse_gradient: f32 is 'host' or 'device'")
+    entry = None
+    if (is_native and len(sv) >= 1 and opt.control == "auto" and opt.replay_dts is None
+            and opt.replay_adjoint_dts is None):
+        if p.dtype == torch.float64 and f.hd.trajectories_gradient_supported():
+            entry = f.hd.trajectories_gradient_tsit5
+        elif p.dtype == torch.float32 and f32 == "device" and f.hd.trajectories_gradient_f32_supported():
+            entry = f.hd.trajectories_gradient_f32_tsit5
+    if entry is not None:
         pc, u0c, tc, oc = p.contiguous(), u0.contiguous(), target.contiguous(), opt.to_c()
         if R <= TRAJECTORIES_GRADIENT_MAX:
-            loss, dp, info = f.hd.trajectories_gradient_tsit5(pc, u0c, t0, tf, sv, tc, oc, rows=rows)
+            loss, dp, info = entry(pc, u0c, t0, tf, sv, tc, oc, rows=rows)
         else:   # one call per 65536 trajectories, their rows combined here in the same order
             parts = []
             info = {"fwd_stats": [], "adj_stats": [], "stop": []}
             for a in range(0, R, TRAJECTORIES_GRADIENT_MAX):
                 b = min(R, a + TRAJECTORIES_GRADIENT_MAX)
-                _, _, inf = f.hd.trajectories_gradient_tsit5(pc, u0c[a:b], t0, tf, sv, tc[:, a:b].contiguous(), oc,
-                                                             rows=True)
+                _, _, inf = entry(pc, u0c[a:b], t0, tf, sv, tc[:, a:b].contiguous(), oc, rows=True)
                 parts.append(torch.cat([inf["dp_rows"], inf["loss_rows"][:, None]], dim=1))
                 for k in ("fwd_stats", "adj_stats", "stop"):
                     info[k] += inf[k]

@@ -414,6 +414,11 @@ class KanodeHandle:
         "loss_rows" [R] (rows), "du0" [R, N], "u_save" [len(saveat), R, N] (pre-filled with NaN).  A trajectory that
         stops does not raise: stop[r] names the reason, its rows are NaN and so are loss and dp.  An unsupported handle
         or a bad argument raises KanodeError."""
+        return self._trajectories_gradient("kanode_trajectories_gradient_tsit5", p, u0, t0, tf, saveat, target, opts,
+                                           rows, du0, u_save)
+
+    def _trajectories_gradient(self, _entry, p, u0, t0, tf, saveat, target, opts, rows, du0, u_save):
+        """The call of either entry (the fp64 one or kanode_trajectories_gradient_f32_tsit5): same arguments."""
         self._check_t(p, (self.P,), "p")
         if u0.dim() != 2:
             raise ValueError("trajectories_gradient_tsit5 needs u0 of shape [R, N]")
@@ -437,10 +442,10 @@ class KanodeHandle:
         fst = (L.SolveStatsC * max(R, 1))()
         ast = (L.SolveStatsC * max(R, 1))()
         stop = (C.c_int32 * max(R, 1))()
-        L.check(L.lib().kanode_trajectories_gradient_tsit5(
+        L.check(getattr(L.lib(), _entry)(
             self._h, _ptr(p), _ptr(u0), R, float(t0), float(tf), sv, len(saveat), _ptr(target), C.byref(opts),
             C.byref(loss), _ptr(dp), _ptr(out_rows), _ptr(out_loss), _ptr(out_du0), _ptr(out_us), fst, ast,
-            stop, _stream(self.device)), self._h, "kanode_trajectories_gradient_tsit5")
+            stop, _stream(self.device)), self._h, _entry)
         info = {"fwd_stats": [dict(naccept=fst[r].naccept, nreject=fst[r].nreject, nf=fst[r].nf) for r in range(R)],
                 "adj_stats": [dict(naccept=ast[r].naccept, nreject=ast[r].nreject, nf=ast[r].nf) for r in range(R)],
                 "stop": [L.TRAIN_STOP.get(int(stop[r]), str(stop[r])) for r in range(R)]}
@@ -451,6 +456,25 @@ class KanodeHandle:
         if u_save:
             info["u_save"] = out_us
         return float(loss.value), dp, info
+
+    def trajectories_gradient_f32_supported(self) -> bool:
+        """kanode_trajectories_gradient_f32_supported: the fp32 trajectory-ensemble gradient covers this handle (an
+        fp32 chain of the one-workgroup solve at batch 1 whose fp32 column-group adjoint fits one wave: P even;
+        fused_solve on)."""
+        return bool(L.lib().kanode_trajectories_gradient_f32_supported(self._h))
+
+    def trajectories_gradient_f32_group(self, t0: float, tf: float, n_save: int, opts: "L.SolverOptsC") -> int:
+        """kanode_trajectories_gradient_f32_group: trajectories_gradient_group for the fp32 entry.  0: not covered."""
+        return int(L.lib().kanode_trajectories_gradient_f32_group(self._h, float(t0), float(tf), int(n_save),
+                                                                  C.byref(opts)))
+
+    def trajectories_gradient_f32_tsit5(self, p: torch.Tensor, u0: torch.Tensor, t0: float, tf: float, saveat,
+                                        target: torch.Tensor, opts: "L.SolverOptsC", rows: bool = False,
+                                        du0: bool = False, u_save: bool = False):
+        """trajectories_gradient_tsit5 on an fp32 handle (kanode_trajectories_gradient_f32_tsit5): the same arguments
+        and the same (loss, dp, info), every tensor float32; loss is the float total as a Python float."""
+        return self._trajectories_gradient("kanode_trajectories_gradient_f32_tsit5", p, u0, t0, tf, saveat, target,
+                                           opts, rows, du0, u_save)
 
     def _saveat_c(self, saveat):
         key = tuple(saveat)

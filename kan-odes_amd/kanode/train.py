@@ -658,12 +658,15 @@ class TrajectoryTrainer:
 
     loss_and_grad() adds the L1 term of sparse_reg on the host by Trainer's formula; step() is one Adam update
     (kanode_adam_step on the GPU) and raises KanodeError before it when any trajectory stopped, leaving p and the
-    moments as they were.  One process: a data-parallel split over trajectories is not part of this class."""
+    moments as they were.  One process: a data-parallel split over trajectories is not part of this class.
+    f32 is passed to trajectories_mse_gradient: "device" runs float32 parameters on the fp32 one-launch entry where the
+    handle covers the chain (off by default; a later change may flip it)."""
 
     def __init__(self, rhs, u0, tspan, saveat, target, p0, eta: float = 5e-4, solver: Tsit5Options | None = None,
-                 sparse_reg: float = 0.0):
+                 sparse_reg: float = 0.0, f32: str = "host"):
         if not isinstance(u0, torch.Tensor) or u0.dim() != 2:
             raise ValueError("TrajectoryTrainer: u0 must be a tensor of shape [R, N]")
+        self.f32 = f32   # what trajectories_mse_gradient does with float32 parameters ("host" / "device")
         self.rhs, self.u0, self.tspan, self.saveat, self.target = rhs, u0, tspan, saveat, target
         self.p = p0.detach().clone()
         self.opt = FusedAdam(eta) if self.p.is_cuda else Adam(eta)
@@ -681,7 +684,7 @@ class TrajectoryTrainer:
         """(loss (0-dim tensor), gradient [P], info) at the current parameters."""
         from .adjoint import trajectories_mse_gradient
         loss, g, info = trajectories_mse_gradient(self.rhs, self.u0, self.tspan, self.p, self.saveat, self.target,
-                                                  self.solver)
+                                                  self.solver, f32=self.f32)
         self.last_info = info
         loss = torch.as_tensor(loss, dtype=g.dtype, device=g.device)
         if self.sparse_reg:   # (Trainer._with_l1's statements)
